@@ -6,11 +6,17 @@ each rank owns its own pre-sharded 1M batch (values are independent, so there is
 collective), and `value` = all ranks' blob bytes / max-over-ranks time.
 
 A step = one rr_decode_batch call (look-back reset + one decode launch) over the whole batch.
-Also reported: encode throughput (same batch), the roofline of the decode kernel (algorithmic
-bytes per launch / launch time vs 8 TB/s HBM3E) and, on rank 0 at N=1, the CPU baseline: the
-reference-faithful desObject restatement (oracle/rro_faithful.c) on the box's host cores.
+A plain run does only what that figure needs: it generates the batch, warms up, times --steps
+decode steps and prints the result line, with the roofline of the decode kernel (algorithmic
+bytes per launch / launch time vs 8 TB/s HBM3E) priced from the same timed steps.
+`--dump-outputs DIR` also writes what the last timed step decoded to DIR/*.npy (dump_outputs).
+`--full` adds every other leg to the line: encode throughput (same batch), the device copy and
+PCIe-inclusive host legs, the round-trip and oracle checks of what was timed, the RCCL
+split/gather leg, the snappy leg and, on rank 0 at N=1, the CPU baseline: the reference-faithful
+desObject restatement (oracle/rro_faithful.c) on the host's cores.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--n VALUES] [--config 4]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--n VALUES] [--config 4] [--full]
+        [--dump-outputs DIR]
 Multi-GPU: `python bench.py --gpus N` starts its N ranks itself (one process per GPU, a
 torch.distributed.run child process started before anything touches the GPU; this process only
 waits for it and exits with its code), or run it under an outside launcher:
@@ -49,12 +55,19 @@ def parse():
     p.add_argument("--shards", type=int, default=8, help="config 5: shards of the byte-balanced plan")
     p.add_argument("--shard-index", type=int, default=None,
                    help="config 5: the shard this rank decodes (default: its rank; the last shard at N=1)")
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="budget for the CPU baseline leg")
-    p.add_argument("--no-cpu", action="store_true")
-    p.add_argument("--no-check", action="store_true")
-    p.add_argument("--no-host", action="store_true", help="skip the PCIe-inclusive host leg and the copy reference")
-    p.add_argument("--no-split", action="store_true", help="skip the RCCL root split/gather leg")
-    p.add_argument("--no-snappy", action="store_true", help="skip the snappy block-compression leg (row f3)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed decode also run the encode leg, the copy and host (PCIe) reference legs, "
+                        "the round-trip and oracle checks, the RCCL split/gather leg, the snappy leg and the CPU "
+                        "baseline, and report them in the result line (the --no-* options trim this set)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last decode step left in the caller's buffers "
+                        "to DIR/<name>.npy (see dump_outputs)")
+    p.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget for the CPU baseline leg")
+    p.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline legs")
+    p.add_argument("--no-check", action="store_true", help="--full: skip the round-trip and oracle checks")
+    p.add_argument("--no-host", action="store_true", help="--full: skip the PCIe-inclusive host legs")
+    p.add_argument("--no-split", action="store_true", help="--full: skip the RCCL root split/gather leg")
+    p.add_argument("--no-snappy", action="store_true", help="--full: skip the snappy block-compression leg (row f3)")
     p.add_argument("--profile-only", action="store_true", help="decode steps only (for rocprofv3)")
     p.add_argument("--profile-encode", action="store_true", help="one decode, then encode steps only (for rocprofv3)")
     p.add_argument("--plan-only", action="store_true", help="print the launch decision and rank layout, no GPU call")
@@ -170,6 +183,12 @@ def main():
     import redrock_old_amd as rr
 
     world, rank, local = plan["world"], plan["rank"], plan["local_rank"]
+    if not args.full and rank == 0:
+        unused = [o for o in ("--no-cpu", "--no-check", "--no-host", "--no-split", "--no-snappy", "--cpu-seconds")
+                  if any(a == o or a.startswith(o + "=") for a in sys.argv[1:])]
+        if unused:
+            print(f"bench.py: {' '.join(unused)}: only --full runs the legs these options trim; ignored",
+                  file=sys.stderr)
     if world > 1:
         torch.cuda.set_device(local)
         dist.init_process_group("nccl", device_id=torch.device(f"cuda:{local}"))
@@ -259,25 +278,31 @@ def main():
     wall_dec, ev_dec = timed(decode, args.steps, args.warmup)
     tot = d_tot.cpu().numpy().view(np.uint64).copy()
     n_elems, n_bad, payload = int(tot[0]), int(tot[2]), int(tot[3])
-    wall_enc, ev_enc = timed(encode, args.steps, args.warmup)
-    tot2 = d_tot2.cpu().numpy().view(np.uint64).copy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, tot, d_vals, d_elems, d_arena, n, n_elems, nb)
 
-    # ---- reference legs (not the headline): device copy bandwidth, PCIe-inclusive decode ----
-    # the engine's own streaming copy (rr_copy_device: the decode window copy's load/store
-    # shape) is the measured ceiling the roofline is also priced against; torch's copy beside it
-    d_copy = torch.zeros_like(d_data)
-    _, ev_rrcopy = timed(lambda: eng.copy_device(d_copy, d_data, stream=stream), args.steps, args.warmup)
-    copy_ok = bool(torch.equal(d_copy, d_data))
-    _, ev_copy = timed(lambda: d_copy.copy_(d_data), args.steps, args.warmup)
-    del d_copy
-    rrcopy_gbs = 2 * d_data.numel() / (ev_rrcopy * 1e-3) / 1e9   # read + write
-    copy_gbs = 2 * d_data.numel() / (ev_copy * 1e-3) / 1e9
-    copy_ref = {"GBs": round(rrcopy_gbs, 1), "frac_of_peak": round(rrcopy_gbs / HBM_PEAK_GBS, 4),
-                "ms": round(ev_rrcopy, 4), "bit_exact": copy_ok,
-                "what": "rr_copy_device (the engine's streaming copy kernel) of the blob buffer, read + write bytes",
-                "torch_copy_GBs": round(copy_gbs, 1)}
+    # ---- a plain run ends here: its result line is the timed decode alone.  --full adds the
+    # ---- encode leg, the reference legs, the correctness checks and the CPU baseline
+    if args.full:
+        wall_enc, ev_enc = timed(encode, args.steps, args.warmup)
+        tot2 = d_tot2.cpu().numpy().view(np.uint64).copy()
+
+        # ---- reference legs (not the headline): device copy bandwidth, PCIe-inclusive decode ----
+        # the engine's own streaming copy (rr_copy_device: the decode window copy's load/store
+        # shape) is the measured ceiling the roofline is also priced against; torch's copy beside it
+        d_copy = torch.zeros_like(d_data)
+        _, ev_rrcopy = timed(lambda: eng.copy_device(d_copy, d_data, stream=stream), args.steps, args.warmup)
+        copy_ok = bool(torch.equal(d_copy, d_data))
+        _, ev_copy = timed(lambda: d_copy.copy_(d_data), args.steps, args.warmup)
+        del d_copy
+        rrcopy_gbs = 2 * d_data.numel() / (ev_rrcopy * 1e-3) / 1e9   # read + write
+        copy_gbs = 2 * d_data.numel() / (ev_copy * 1e-3) / 1e9
+        copy_ref = {"GBs": round(rrcopy_gbs, 1), "frac_of_peak": round(rrcopy_gbs / HBM_PEAK_GBS, 4),
+                    "ms": round(ev_rrcopy, 4), "bit_exact": copy_ok,
+                    "what": "rr_copy_device (the engine's streaming copy kernel) of the blob buffer, read + write bytes",
+                    "torch_copy_GBs": round(copy_gbs, 1)}
     host = None
-    if not args.no_host:
+    if args.full and not args.no_host:
         # one step = pinned H2D of blobs + offsets, the decode, pinned D2H of records,
         # descriptors and arena (what rr_decode_batch_host does, through pinned buffers)
         h_data = torch.from_numpy(data).pin_memory()
@@ -349,7 +374,7 @@ def main():
 
     # ---- correctness of what was timed ----
     parity = None
-    if not args.no_check:
+    if args.full and not args.no_check:
         rt = bool(torch.equal(d_out[:nb], d_data[:nb])) and bool(
             np.array_equal(d_ooffs.cpu().numpy().view(np.uint64), offs))
         parity = {"roundtrip_bit_exact": rt, "n_bad": n_bad}
@@ -368,14 +393,12 @@ def main():
     ms_step = wall_dec / args.steps * 1e3
     gib_s = tot_bytes * args.steps / wall_dec / 2 ** 30
     vals_s = tot_vals * args.steps / wall_dec
-    enc_gib_s = tot_bytes * args.steps / wall_enc / 2 ** 30
 
-    # roofline of the decode kernel (SURVEY.md §8d algorithmic bytes, per launch, this rank)
+    # roofline of the decode kernel (SURVEY.md §8d algorithmic bytes, per launch, this rank),
+    # from the timed steps' own HIP events; frac_of_copy needs the copy leg, so --full adds it
     alg_bytes = nb + 16 * n + 16 * n_elems + payload
     traffic = measured_traffic(args.config, n, nb)
     achieved = alg_bytes / (ev_dec * 1e-3) / 1e9
-    enc_alg = 16 * n + 16 * n_elems + int(tot2[3]) + nb + 8 * (n + 1)
-    enc_achieved = enc_alg / (ev_enc * 1e-3) / 1e9
 
     result = {
         "metric": METRIC,
@@ -398,22 +421,30 @@ def main():
         "values_per_s": round(vals_s, 1),
         "decode": {"gib_s": round(gib_s, 2), "values_per_s": round(vals_s, 1), "ms_per_step": round(ms_step, 4),
                    "event_ms_per_launch": round(ev_dec, 4)},
-        "encode": {"gib_s": round(enc_gib_s, 2), "ms_per_step": round(wall_enc / args.steps * 1e3, 4),
-                   "event_ms_per_launch": round(ev_enc, 4),
-                   "roofline_achieved_GBs": round(enc_achieved, 1)},
         "roofline": {"bound": "hbm", "kernel": "rr_decode_batch (count_kernel + decode_kernel)",
                      "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic[0],
                      "traffic_source": traffic[1],
-                     "alg_bytes_per_launch": alg_bytes,
-                     "frac_of_copy": round(achieved / copy_ref["GBs"], 4) if copy_ref["GBs"] else None},
-        "copy_ref": copy_ref,
-        "parity": parity,
-        **(host or {}),
+                     "alg_bytes_per_launch": alg_bytes},
         "gen_s": round(t_gen, 2),
+        "full": bool(args.full),
     }
+    if args.dump_outputs:
+        result["dump_outputs"] = args.dump_outputs
 
-    if not args.no_split:
+    if args.full:
+        enc_gib_s = tot_bytes * args.steps / wall_enc / 2 ** 30
+        enc_alg = 16 * n + 16 * n_elems + int(tot2[3]) + nb + 8 * (n + 1)
+        enc_achieved = enc_alg / (ev_enc * 1e-3) / 1e9
+        result["encode"] = {"gib_s": round(enc_gib_s, 2), "ms_per_step": round(wall_enc / args.steps * 1e3, 4),
+                            "event_ms_per_launch": round(ev_enc, 4),
+                            "roofline_achieved_GBs": round(enc_achieved, 1)}
+        result["roofline"]["frac_of_copy"] = round(achieved / copy_ref["GBs"], 4) if copy_ref["GBs"] else None
+        result["copy_ref"] = copy_ref
+        result["parity"] = parity
+        result.update(host or {})
+
+    if args.full and not args.no_split:
         # a hang in a collective must not hide the headline line, nor pass as success: after
         # --split-timeout rank 0 prints what it has and every rank exits WATCHDOG_EXIT
         def _report():
@@ -428,20 +459,61 @@ def main():
             result["split_gather"] = {"error": repr(ex)[:300]}
         dog.cancel()
 
-    if not args.no_snappy:
+    if args.full and not args.no_snappy:
         try:
             result["snappy"] = snappy_leg(rr, torch, eng, stream, d_data, nb, timed, args,
                                           cpu_too=(rank == 0 and world == 1 and not args.no_cpu))
         except Exception as ex:   # reported, never fatal to the headline
             result["snappy"] = {"error": repr(ex)[:300]}
 
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         result["cpu_baseline"] = cpu_baseline(data, offs, nb, args.cpu_seconds)
 
     if rank == 0:
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_SEED = 20240611                                 # the sample is the same in every run and build
+DUMP_VALUES, DUMP_ELEMS, DUMP_ARENA = 1 << 18, 1 << 19, 1 << 18   # records, descriptors, 16-byte arena chunks
+
+
+def dump_outputs(out_dir, torch, tot, d_vals, d_elems, d_arena, n, n_elems, nb):
+    """--dump-outputs: what the last timed rr_decode_batch call left in the caller's buffers, as
+    DIR/<name>.npy, so that two builds can be compared output for output (the batch is seeded: the
+    same arguments give the same inputs).  Rank 0 alone dumps, so DIR holds one rank's files
+    whatever --gpus is.
+      totals.npy  float64 [4]      n_elems, bytes, n_bad, payload (exact: all below 2^53)
+      values.npy  float64 [k, 4]   value records, each as its four little-endian u32 words
+      elems.npy   float64 [k, 4]   element descriptors (of the n_elems written), same form
+      arena.npy   float32 [k, 16]  16-byte chunks of arena[0, blob bytes), one byte per number; if
+                                   the blob bytes are no multiple of 16, the last row is the tail,
+                                   padded with zeros (always kept, never sampled away)
+    u32 words in float64 and bytes in float32 are exact, so equal files mean equal bits.  A batch
+    past DUMP_VALUES / DUMP_ELEMS / DUMP_ARENA rows is sampled: sorted row numbers drawn (with
+    repetition) from a generator seeded with DUMP_SEED, gathered on the device; 40 MiB at most."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def rows(d_buf, count, width, limit):
+        t = d_buf[: count * width].view(count, width)
+        if count > limit:
+            idx = np.sort(rng.integers(0, count, size=limit, dtype=np.int64))
+            t = t[torch.from_numpy(idx).to(d_buf.device)]
+        return t.cpu().numpy()
+
+    arena = rows(d_arena, nb // 16, 16, DUMP_ARENA)
+    if nb % 16:
+        tail = np.zeros((1, 16), np.uint8)
+        tail[0, : nb % 16] = d_arena[nb // 16 * 16: nb].cpu().numpy()
+        arena = np.concatenate([arena, tail])
+    arrays = {"totals": tot.astype(np.float64),
+              "values": rows(d_vals, n, 16, DUMP_VALUES).view("<u4").astype(np.float64),
+              "elems": rows(d_elems, min(n_elems, d_elems.numel() // 16), 16, DUMP_ELEMS).view("<u4").astype(np.float64),
+              "arena": arena.astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def split_gather_leg(rr, torch, dist, eng, world, rank, dev, stream, d_data, d_offs, d_vals, d_elems, n, nb,

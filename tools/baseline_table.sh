@@ -1,12 +1,14 @@
 #!/bin/bash
-# BASELINE.md's single-GPU rows (GPU box, repo root): one bench.py line per BASELINE config,
-# each with its CPU baseline legs, into gpurun_out/bl/.  usage: tools/baseline_table.sh
-mkdir -p gpurun_out/bl
+# BASELINE.md's single-GPU rows (on the GPU host, repo root): one bench.py --full line per BASELINE
+# config, each with its CPU baseline legs, into $RR_OUT/bl/ (default out/bl/).
+# usage: tools/baseline_table.sh
+OUT=${RR_OUT:-out}/bl
+mkdir -p $OUT
 run() {   # name args...
     local name=$1; shift
-    timeout -k 10 400 python3 -u bench.py --no-split --no-snappy "$@" > gpurun_out/bl/$name.log 2>&1
+    timeout -k 10 400 python3 -u bench.py --full --no-split --no-snappy "$@" > $OUT/$name.log 2>&1
     local rc=$?
-    grep '^{' gpurun_out/bl/$name.log | tail -1 > gpurun_out/bl/$name.json
+    grep '^{' $OUT/$name.log | tail -1 > $OUT/$name.json
     echo "$name rc=$rc"
     return $rc
 }

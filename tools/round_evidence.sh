@@ -1,13 +1,14 @@
 #!/bin/bash
-# The round's profile evidence + bench lines in one GPU call (GPU box, repo root):
-#   gpurun_out/ev/{dec,enc}   rocprofv3 kernel trace + FETCH_SIZE / WRITE_SIZE passes (profile_bench.sh)
-#   gpurun_out/ev/pmc         SQ / TCC counter passes of the decode (pmc_decode.sh)
-#   gpurun_out/ev/*.json      traffic summaries and the bench.py lines (1M default, 10M config 4)
+# The round's profile evidence + bench lines in one GPU call (GPU host, repo root), under
+# $RR_OUT/ev (default out/ev):
+#   ev/{dec,enc}   rocprofv3 kernel trace + FETCH_SIZE / WRITE_SIZE passes (profile_bench.sh)
+#   ev/pmc         SQ / TCC counter passes of the decode (pmc_decode.sh)
+#   ev/*.json      traffic summaries and the bench.py --full lines (1M default, 10M config 4)
 # The decode summary is copied into profiles/ first, so bench.py's roofline.traffic comes
 # from this build.  usage: tools/round_evidence.sh ROUNDTAG (e.g. r2)
 set -e
 R=${1:-r2}
-E=gpurun_out/ev
+E=${RR_OUT:-out}/ev
 mkdir -p $E
 cp profiles/${R}_decode_summary.json $E/${R}_decode_summary.json 2>/dev/null || true
 cp profiles/${R}_encode_summary.json $E/${R}_encode_summary.json 2>/dev/null || true
