@@ -68,6 +68,20 @@ void _test_ser_des_zset(void);
 #define RR_COMPAT_ROUTE_GPU  2
 void rr_compat_set_route(int route);
 
+/* The ziplist check.  Strict (the compiled-in default): desObject and the batch forms walk every
+ * Hash / ZSet ziplist and panic on one whose entries, zltail, zllen or pair count do not parse —
+ * stricter than the reference, which checks only that the stored byte count equals the rest of the
+ * blob and copies the ziplist blind (rock_serdes.c:356-366, :455-466).  Off: exactly the
+ * reference's test, in O(1) — desObject accepts what the reference accepts at the reference's
+ * cost, and the batch forms give the same objects on the host and the GPU route
+ * (RR_CTX_ZL_RAW, rr_serdes.h).  The environment's RR_COMPAT_ZL_CHECK (1 = strict, 0 = off) sets
+ * the default, read at the first call; this call overrides it.  rr_compat_rdb_load_batch applies
+ * the calling process's check to the records the parent's service decoded: strict here, a ziplist
+ * that arrives as its ZLRAW alone (a parent in raw mode) is walked here and a corrupt one panics;
+ * off here, the parent sets RR_CTX_ZL_RAW on the context it gives rr_rdb_serve — a ziplist its
+ * strict walk rejected carries no bytes to rebuild it from, and that pairing panics by name. */
+void rr_compat_set_ziplist_check(int strict);
+
 /* Process exit: every GPU call through this shim is counted in flight; the owner's exit waits
  * (at most 10 s) for the count to drain, and a thread calling in after the exit began parks
  * rather than enter the HIP runtime being torn down (RedRock's rock thread, rock.c:615, is never

@@ -33,7 +33,9 @@
  *                   dictAdd keeps the first and ignores the rest, rock_serdes.c:297); the
  *                   value still owns one slot per blob member, the unused tail is zero
  *   HASH_ZIPLIST    ZLRAW{arena off, L} then one elem per ziplist entry (STR or INT,
- *   ZSET_ZIPLIST    zenc = the entry's encoding byte); encode only needs ZLRAW
+ *   ZSET_ZIPLIST    zenc = the entry's encoding byte); encode only needs ZLRAW.  With
+ *                   RR_CTX_ZL_RAW (rr_serdes.h) decode stops there too: ZLRAW alone, one slot, the
+ *                   bytes unread — what desHash / desZset accept (rock_serdes.c:356-366, :455-466)
  *   HASH_HT         2n STR elems: field, value, field, value, ... (duplicate field: RR_E_DUP)
  *   ZSET_SKIPLIST   2n elems: STR member, SCORE{f64 bits}, ... in the order serZset writes
  *                   the skiplist desZset builds: descending (score, member) (zslInsert,

@@ -88,6 +88,16 @@ int  rr_ctx_reserve(rr_ctx *ctx, uint64_t n_values, uint64_t n_bytes);
  * batch pipeline, also a batch small enough for the one-launch kernels (at most 4096 values in
  * at most 128 KiB: decode by in->data_cap, encode by out->data_cap) — for tests and timing. */
 #define RR_CTX_NO_SMALL 1u
+/* RR_CTX_ZL_RAW: the reference's acceptance rule for Hash / ZSet ziplists (desHash / desZset,
+ * rock_serdes.c:356-366, :455-466).  A type-12/13 blob of L >= 13 bytes whose u64 at byte 5 equals
+ * L - 13 (and fits rr_elem.len) is accepted whatever its bytes are: status RR_OK, n_elems 1, one
+ * slot holding ZLRAW{blob offset + 13, L - 13}, L - 13 counted as payload; no entry walk, no
+ * entry descriptors, no RR_E_ZL_CORRUPT.  A shorter blob and a count that disagrees keep their
+ * statuses (RR_E_SHORT, RR_E_ZL_LEN); every other type is untouched.  Read at every decode call
+ * of the context (rr_decode_batch, rr_decode_batch_host, and rr_kv_restore_batch / rr_rdb_serve
+ * through the context they are given); clearing it restores the default, stricter results.
+ * Encode needs no flag: a ziplist value is written from its ZLRAW alone. */
+#define RR_CTX_ZL_RAW 2u
 int  rr_ctx_set_options(rr_ctx *ctx, unsigned flags);
 const char *rr_last_error(void);
 
@@ -125,6 +135,18 @@ int rr_encode_batch_host(rr_ctx *ctx, const rr_value *values, const rr_elem *ele
                          uint64_t n_elems, const uint8_t *arena, uint64_t arena_bytes,
                          uint64_t n, uint8_t *data, uint64_t data_cap, uint64_t *offsets,
                          rr_totals *totals);
+
+/* ---- the host codec with decode options (rr_host.h) ----------------------------------- */
+/* rr_host_decode_value / rr_host_decode_batch of rr_host.h (the engine's CPU codec: plain C, no
+ * HIP, same records as the GPU entry points) with the RR_CTX_* decode flags of a context:
+ * RR_CTX_ZL_RAW gives the results rr_decode_batch gives on a context that has it set
+ * (RR_CTX_NO_SMALL means nothing here and is ignored; the batch form refuses unknown bits).
+ * With flags 0 they are the rr_host.h functions. */
+int rr_host_decode_value_ex(const uint8_t *blob, uint64_t len, uint64_t base, rr_value *v, rr_elem *el,
+                            uint64_t cap, uint64_t *need, unsigned flags);
+int rr_host_decode_batch_ex(const uint8_t *data, const uint64_t *offsets, uint64_t n, rr_value *values,
+                            rr_elem *elems, uint64_t elem_cap, uint8_t *arena, rr_totals *totals,
+                            unsigned flags);
 
 /* ---- multi-GPU sharding ---------------------------------------------- */
 /* Values are independent: a batch splits into G contiguous value ranges balanced by bytes,

@@ -35,6 +35,8 @@ STATUS_NAMES = {0: "OK", 1: "SHORT", 2: "TYPE", 3: "STR_ENC", 4: "STR_INTLEN", 5
 
 CONFIG_MIXED = 4
 CTX_NO_SMALL = 1          # rr_ctx_set_options: no one-launch small-batch kernels
+CTX_ZL_RAW = 2            # rr_ctx_set_options / the host codec's _ex calls: ziplists kept raw, the
+                          # reference's acceptance rule (one ZLRAW descriptor, no entry walk)
 SMALL_N, SMALL_BYTES = 4096, 128 * 1024   # the one-launch kernels' limits (rr_serdes.h)
 
 
@@ -85,7 +87,8 @@ EXPORTS = ["rr_ctx_create", "rr_ctx_destroy", "rr_ctx_reserve", "rr_last_error",
            "rr_gen_batch", "rr_host_batch_free", "rr_gen_default_seed", "rr_shard_plan", "rr_flat_rebase",
            "rr_comm_get_id", "rr_comm_init", "rr_comm_destroy", "rr_split_plan", "rr_split", "rr_gather",
            "rr_flat_rebase_host", "rr_gather_layout", "rr_copy_device", "rr_gen_sizes", "rr_gen_range",
-           "rr_split_schedule", "rr_gather_schedule", "rr_ctx_set_options"]
+           "rr_split_schedule", "rr_gather_schedule", "rr_ctx_set_options", "rr_host_decode_value_ex",
+           "rr_host_decode_batch_ex"]
 COMM_ID_BYTES = 128
 # include/rr_snappy.h (GPU block compression)
 SNAPPY_EXPORTS = ["rr_snappy_max_compressed_length", "rr_snappy_compress_bound", "rr_snappy_compress_batch",
@@ -175,6 +178,11 @@ def lib():
         L.rr_host_encode_value.argtypes = [vp, vp, vp, vp]
         L.rr_host_encode_value.restype = None
         L.rr_host_encode_batch.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, vp, C.POINTER(Totals)]
+        # (the product library must export them: a missing one fails here, at load; only an older
+        #  build named by RR_LIB for A/B timing may predate them)
+        if "RR_LIB" not in os.environ or hasattr(L, "rr_host_decode_batch_ex"):
+            L.rr_host_decode_value_ex.argtypes = [vp, u64, u64, vp, vp, u64, C.POINTER(C.c_uint64), C.c_uint]
+            L.rr_host_decode_batch_ex.argtypes = [vp, vp, u64, vp, vp, u64, vp, C.POINTER(Totals), C.c_uint]
     _lib = L
     return L
 
@@ -319,6 +327,34 @@ def host_decode_value(blob: bytes, base: int = 0, cap: int = 64):
     return int(st), v[0], e[:min(int(v[0]["n_elems"]), cap)], int(need.value)
 
 
+def host_decode_ex(data: np.ndarray, offsets: np.ndarray, flags: int, elem_cap: int | None = None):
+    """rr_host_decode_batch_ex: host_decode with the RR_CTX_* decode flags (CTX_ZL_RAW)."""
+    n = len(offsets) - 1
+    nbytes = int(offsets[-1])
+    if elem_cap is None:
+        elem_cap = elem_bound(n, nbytes)
+    data = np.ascontiguousarray(data, np.uint8)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    values = np.zeros(n, VALUE_DT)
+    elems = np.zeros(max(elem_cap, 1), ELEM_DT)
+    arena = np.zeros(max(nbytes, 1), np.uint8)
+    t = Totals()
+    _check(lib().rr_host_decode_batch_ex(_ptr(data), _ptr(offsets), n, _ptr(values), _ptr(elems), elem_cap,
+                                         _ptr(arena), C.byref(t), flags))
+    ne = min(int(t.n_elems), elem_cap)
+    return values, elems[:ne], arena[:nbytes], t.as_dict()
+
+
+def host_decode_value_ex(blob: bytes, flags: int, base: int = 0, cap: int = 64):
+    """rr_host_decode_value_ex: host_decode_value with the RR_CTX_* decode flags (CTX_ZL_RAW)."""
+    b = np.frombuffer(bytes(blob) or b"\0", np.uint8)
+    v = np.zeros(1, VALUE_DT)
+    e = np.zeros(max(cap, 1), ELEM_DT)
+    need = C.c_uint64()
+    st = lib().rr_host_decode_value_ex(_ptr(b), len(blob), base, _ptr(v), _ptr(e), cap, C.byref(need), flags)
+    return int(st), v[0], e[:min(int(v[0]["n_elems"]), cap)], int(need.value)
+
+
 def host_check(data: np.ndarray, offsets: np.ndarray) -> np.ndarray:
     """rr_host_check_value per blob: the records (elem_base 0) rr_host_decode_value gives."""
     data = np.ascontiguousarray(data, np.uint8)
@@ -372,7 +408,8 @@ class Engine:
             pass
 
     def set_options(self, flags: int):
-        """RR_CTX_* flags (CTX_NO_SMALL: every call takes the batch pipeline)."""
+        """RR_CTX_* flags (CTX_NO_SMALL: every call takes the batch pipeline; CTX_ZL_RAW: decode
+        keeps Hash / ZSet ziplists raw, the reference's acceptance rule).  Read at every call."""
         _check(self._L.rr_ctx_set_options(self._ctx, flags))
 
     def debug_fail_second(self):

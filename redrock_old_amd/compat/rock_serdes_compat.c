@@ -69,6 +69,22 @@ static void read_config(void) {
 
 void rr_compat_set_route(int route) { g_route = route; }
 
+/* The ziplist check of desObject and the batch forms: strict (the default) walks every Hash / ZSet
+ * ziplist and panics on one that does not parse; off is the reference's own rule — the stored byte
+ * count equals the rest of the blob, then a blind copy (rock_serdes.c:356-366, :455-466).
+ * -1 = not read yet: the environment's RR_COMPAT_ZL_CHECK ("0" = off), else strict. */
+static int g_zl_strict = -1;
+void rr_compat_set_ziplist_check(int strict) { __atomic_store_n(&g_zl_strict, strict ? 1 : 0, __ATOMIC_RELAXED); }
+static inline int zl_strict(void) {
+    int s = __atomic_load_n(&g_zl_strict, __ATOMIC_RELAXED);
+    if (__builtin_expect(s < 0, 0)) {
+        const char *e = getenv("RR_COMPAT_ZL_CHECK");
+        s = !(e && e[0] == '0' && !e[1]);
+        __atomic_store_n(&g_zl_strict, s, __ATOMIC_RELAXED);
+    }
+    return s;
+}
+
 static pid_t g_owner;    /* the process whose threads own GPU contexts */
 static int g_forked;     /* this process is a fork child of an owner (its HIP runtime is the parent's) */
 static int g_as_child;   /* test hook: route this process as a fork child would */
@@ -297,6 +313,26 @@ static robj *des_host(const void *buf, size_t len) {
     uint64_t need;
     const uint8_t *b = buf;
     if (len >= 13 && (b[0] == RR_TYPE_HASH_ZIPLIST || b[0] == RR_TYPE_ZSET_ZIPLIST)) {
+        uint64_t L;
+        memcpy(&L, b + 5, 8);
+        if (!zl_strict() && L <= 0xFFFFFFFFull) {
+            /* the check off: serverAssert(len == zip_list_bytes_len) and the copy (:360-363, :459-462),
+             * the record RR_CTX_ZL_RAW gives — nothing reads the ziplist's bytes */
+            if (L != len - 13)
+                serverPanic("desObject: bad blob (%s, status %u)", status_name(RR_E_ZL_LEN), (unsigned)RR_E_ZL_LEN);
+            uint32_t lru;
+            memcpy(&lru, b + 1, 4);
+            v.type = b[0];
+            v.enc = 0;
+            v.status = RR_OK;
+            v.lru = lru & RR_LRU_MASK;
+            v.n_elems = 1;
+            v.elem_base = 0;
+            local[0].kind = RR_K_ZLRAW;
+            local[0].data = 13;
+            local[0].len = (uint32_t)L;
+            return robj_from_flat(&v, local, b, b);
+        }
         /* kept as its raw bytes (:356-366, :455-466): the ziplist's verdict, no entry descriptors */
         const int st = rr_host_check_value(b, len, &v);
         if (st != RR_OK) serverPanic("desObject: bad blob (%s, status %u)", status_name((unsigned)st), (unsigned)st);
@@ -333,8 +369,11 @@ static void des_batch_gpu(void *const *bufs, const size_t *lens, size_t n, robj 
     rr_elem *els = zmalloc(sizeof(rr_elem) * (cap ? cap : 1));
     rr_totals t;
     engine_enter();
+    /* the ziplist check is the host route's (results equal on either route); read per call */
+    rr_ctx *ctx = engine();
+    int rc = rr_ctx_set_options(ctx, zl_strict() ? 0u : RR_CTX_ZL_RAW);
     /* no arena download: it would mirror `data` byte for byte, so the descriptors index it */
-    const int rc = rr_decode_batch_host(engine(), data, offs, n, vals, els, cap, NULL, &t);
+    if (rc == RR_API_OK) rc = rr_decode_batch_host(ctx, data, offs, n, vals, els, cap, NULL, &t);
     engine_leave();
     if (rc != RR_API_OK) serverPanic("desObject: %s", rr_last_error());
     for (size_t i = 0; i < n; i++) {
@@ -359,7 +398,28 @@ void rr_compat_rdb_load_batch(int fd_req, int fd_resp, int dbid, sds *keys, size
     rr_rdb_flat f;
     if (rr_rdb_request_flat(fd_req, fd_resp, dbis, (const char *const *)keys, lens, k, &f) != RR_API_OK || f.n != k)
         serverPanic("rock rdb batch restore: %s", rr_last_error());
+    /* The records are the parent's decode (the context it gave rr_rdb_serve), the ziplist check is
+     * this process's: it is applied here, so the objects are the ones this process's desObject
+     * builds whatever mode the parent's context was in.  Strict here: a ziplist that came as its
+     * ZLRAW alone (a parent in raw mode, or an empty ziplist) is walked now.  Off here: a ziplist
+     * the parent's strict walk rejected cannot be rebuilt — a rejected value has no descriptor,
+     * and the response carries no offsets to find its bytes by — so that pairing ends in a panic
+     * that names it (the parent sets RR_CTX_ZL_RAW on its context). */
+    const int strict = zl_strict();
     for (size_t i = 0; i < k; i++) {
+        const rr_value *v = &f.values[i];
+        const int zl = v->type == RR_TYPE_HASH_ZIPLIST || v->type == RR_TYPE_ZSET_ZIPLIST;
+        if (zl && !strict && v->status == RR_E_ZL_CORRUPT)
+            serverPanic("rock rdb batch restore: the ziplist check is off here but the parent's service decoded with it on "
+                        "(set RR_CTX_ZL_RAW on the context given to rr_rdb_serve)");
+        if (zl && strict && v->status == RR_OK && v->n_elems == 1) {
+            const rr_elem *e = &f.elems[v->elem_base];
+            rr_value w;
+            if (e->kind != RR_K_ZLRAW || e->data < 13 || e->data + e->len > f.bytes)
+                serverPanic("rock rdb batch restore: bad ziplist descriptor");
+            const int st = rr_host_check_value(f.arena + e->data - 13, (uint64_t)e->len + 13, &w);
+            if (st != RR_OK) serverPanic("desObject: bad blob (%s, status %u)", status_name((unsigned)st), (unsigned)st);
+        }
         if (f.values[i].status != RR_OK)   /* desObject's assert sites, as in rr_compat_des_batch */
             serverPanic("desObject: bad blob (%s, status %u)", status_name(f.values[i].status), f.values[i].status);
         out[i] = robj_from_flat(&f.values[i], f.elems + f.values[i].elem_base, f.arena, NULL);

@@ -170,7 +170,7 @@ int rr_mark_scratch(rr_ctx *c, hipStream_t stream) {
 }
 
 int rr_ctx_set_options(rr_ctx *c, unsigned flags) {
-    if (!c || (flags & ~RR_CTX_NO_SMALL)) return fail(RR_API_EINVAL, "rr_ctx_set_options: bad argument");
+    if (!c || (flags & ~(RR_CTX_NO_SMALL | RR_CTX_ZL_RAW))) return fail(RR_API_EINVAL, "rr_ctx_set_options: bad argument");
     c->options = flags;
     return RR_API_OK;
 }
@@ -221,7 +221,7 @@ int rr_decode_batch(rr_ctx *c, const rr_blob_batch *in, rr_flat_batch *out, rr_t
     HIPCHK(hipSetDevice(c->device));   /* (the launch helpers' per-device facts: this context's device) */
     if (SMALL_DEC(c, in->n, in->data_cap)) {   /* one launch, no scratch */
         HIPCHK(rr_launch_decode_small(in->data, in->offsets, in->n, out->values, out->elems, out->elem_cap, out->arena,
-                                      in->data_cap, d_totals, NULL, 0, (hipStream_t)stream));
+                                      in->data_cap, d_totals, NULL, 0, c->options & RR_CTX_ZL_RAW, (hipStream_t)stream));
         return RR_API_OK;
     }
     const uint64_t nsums = rr_decode_sums_words(in->data_cap);
@@ -248,7 +248,7 @@ int rr_decode_batch(rr_ctx *c, const rr_blob_batch *in, rr_flat_batch *out, rr_t
     }
     const hipError_t e = rr_launch_decode(in->data, in->offsets, in->n, out->values, out->elems, out->elem_cap,
                                           out->arena, c->scratch, use, zero, nzero, in->data_cap, d_totals,
-                                          (hipStream_t)stream, first_only);
+                                          (hipStream_t)stream, first_only, c->options & RR_CTX_ZL_RAW);
     rc = mark_scratch(c, (hipStream_t)stream);
     if (e != hipSuccess || first_only == 1) {
         c->dsums_dirty = 1;
@@ -505,7 +505,7 @@ static int decode_host_small(rr_ctx *c, const uint8_t *data, const uint64_t *off
     __atomic_store_n((uint32_t *)(h + o_flag), 0u, __ATOMIC_RELAXED);
     HIPCHK(rr_launch_decode_small(d + o_dat, (const uint64_t *)(d + o_off), n, (rr_value *)(d + o_val),
                                   (rr_elem *)(d + o_el), elem_cap, NULL, AL16(bytes), (rr_totals *)(d + o_tot),
-                                  (uint32_t *)(d + o_flag), seq, c->sstream));
+                                  (uint32_t *)(d + o_flag), seq, c->options & RR_CTX_ZL_RAW, c->sstream));
     rc = small_wait(c, (const uint32_t *)(h + o_flag), seq);
     if (rc) return rc;
     rr_totals t;

@@ -248,8 +248,14 @@ struct Head {
 };
 
 // ---- String (rock_serdes.c:114-158): enc INT -> inline i64, RAW/EMBSTR -> bytes 6..L
+// Also the class of a Hash / ZSet ziplist kept raw (RR_CTX_ZL_RAW: only then does a ziplist type
+// reach this class; its byte count was checked against L by the classifier): the ZLRAW of bytes
+// 13..L, as desHash / desZset copy them (:356-366, :455-466).
 __device__ __forceinline__ void do_string(const Head &H, const Lane &l, uint64_t &pay) {
-    if (H.b5() == RR_ENC_INT) {
+    if (H.type() != RR_TYPE_STRING) {
+        put_desc(l.E, l.slot(0), l.B + l.q + 13, l.L - 13, RR_K_ZLRAW, 0);
+        pay += l.L - 13;
+    } else if (H.b5() == RR_ENC_INT) {
         put_desc(l.E, l.slot(0), (uint64_t)ab(H.h[2], H.h[1], 2) | ((uint64_t)ab(H.h[3], H.h[2], 2) << 32), 0, RR_K_INT, 0);
     } else {
         put_desc(l.E, l.slot(0), l.B + l.q + 6, l.L - 6, RR_K_STR, 0);

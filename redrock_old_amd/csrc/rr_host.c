@@ -126,7 +126,9 @@ static uint64_t zl_walk_count(const uint8_t *zl, uint64_t L) {
     return n;
 }
 
-uint64_t rr_host_reserve(const uint8_t *b, uint64_t len) {
+/* flags: RR_CTX_ZL_RAW = a Hash / ZSet ziplist whose byte count equals the rest of the blob owns
+ * one slot, its ZLRAW (the reference's acceptance rule, rock_serdes.c:360, :459) */
+static uint64_t reserve_fl(const uint8_t *b, uint64_t len, unsigned flags) {
     if (len < 5) return 0;
     if (b[0] == RR_TYPE_STRING) return len >= 6;
     if (b[0] == RR_TYPE_LIST_QUICKLIST) {   /* the length chain up to its first break */
@@ -152,6 +154,7 @@ uint64_t rr_host_reserve(const uint8_t *b, uint64_t len) {
     case RR_TYPE_HASH_ZIPLIST:
     case RR_TYPE_ZSET_ZIPLIST: {
         const uint64_t L = rd64(b + 5);
+        if ((flags & RR_CTX_ZL_RAW) && L == body && L <= 0xFFFFFFFFull) return 1;
         if (L != body || L < 11) return 0;
         const uint64_t zllen = (uint64_t)b[21] | ((uint64_t)b[22] << 8);
         if (zllen == 0xFFFF) return 1 + zl_walk_count(b + 13, L);
@@ -161,6 +164,8 @@ uint64_t rr_host_reserve(const uint8_t *b, uint64_t len) {
     default: return 0;
     }
 }
+
+uint64_t rr_host_reserve(const uint8_t *b, uint64_t len) { return reserve_fl(b, len, 0); }
 
 /* ---------------------------------------------------------------- decode */
 
@@ -448,8 +453,11 @@ static int is_nan_bits(uint64_t s) { return (s & 0x7FF0000000000000ull) == 0x7FF
  * the value owns when valid (SET_HT: one per blob member, duplicates included), *payload = the
  * payload bytes its descriptors reference.  Structural defects (SHORT / TRUNC / COUNT / ...) are
  * reported before DUP / NAN, and a value that needs more than E->cap slots returns
- * RR_E_CAPACITY only once its structure is known good. */
-static int decode_one(emit_t *E, uint64_t len, rr_value *v, uint64_t *slots, uint64_t *payload) {
+ * RR_E_CAPACITY only once its structure is known good.  flags: RR_CTX_ZL_RAW = a ziplist whose
+ * byte count equals the rest of the blob is accepted unread, as its ZLRAW alone (desHash /
+ * desZset, rock_serdes.c:356-366, :455-466); a count that does not fit rr_elem.len keeps the walk's
+ * verdict. */
+static int decode_one(emit_t *E, uint64_t len, rr_value *v, uint64_t *slots, uint64_t *payload, unsigned flags) {
     const uint8_t *b = E->b;
     int st = RR_OK;
     uint64_t pay = 0, nslots = 0;
@@ -548,6 +556,7 @@ static int decode_one(emit_t *E, uint64_t len, rr_value *v, uint64_t *slots, uin
         const uint64_t L = rd64(b + p);
         if (rem - 8 != L) { st = RR_E_ZL_LEN; break; }
         put(E, RR_K_ZLRAW, E->base + 13, (uint32_t)L, 0);   /* the raw ziplist, then its entries */
+        if ((flags & RR_CTX_ZL_RAW) && L <= 0xFFFFFFFFull) { pay = L; break; }
         st = zl_entries(E, 13, L);
         if (st == RR_OK) pay = L;
         break;
@@ -597,13 +606,18 @@ done:
     return st;
 }
 
-int rr_host_decode_value(const uint8_t *blob, uint64_t len, uint64_t base, rr_value *v, rr_elem *el, uint64_t cap,
-                         uint64_t *need) {
+int rr_host_decode_value_ex(const uint8_t *blob, uint64_t len, uint64_t base, rr_value *v, rr_elem *el, uint64_t cap,
+                            uint64_t *need, unsigned flags) {
     emit_t E = {blob, base, el, cap, 0};
     uint64_t slots, pay;
-    const int st = decode_one(&E, len, v, &slots, &pay);
+    const int st = decode_one(&E, len, v, &slots, &pay, flags);
     if (need) *need = st == RR_OK || st == RR_E_CAPACITY ? slots : 0;
     return st;
+}
+
+int rr_host_decode_value(const uint8_t *blob, uint64_t len, uint64_t base, rr_value *v, rr_elem *el, uint64_t cap,
+                         uint64_t *need) {
+    return rr_host_decode_value_ex(blob, len, base, v, el, cap, need, 0);
 }
 
 int rr_host_check_value(const uint8_t *blob, uint64_t len, rr_value *v) {
@@ -629,9 +643,10 @@ int rr_host_check_value(const uint8_t *blob, uint64_t len, rr_value *v) {
     return st;
 }
 
-int rr_host_decode_batch(const uint8_t *data, const uint64_t *offsets, uint64_t n, rr_value *values, rr_elem *elems,
-                         uint64_t elem_cap, uint8_t *arena, rr_totals *totals) {
+int rr_host_decode_batch_ex(const uint8_t *data, const uint64_t *offsets, uint64_t n, rr_value *values, rr_elem *elems,
+                            uint64_t elem_cap, uint8_t *arena, rr_totals *totals, unsigned flags) {
     if ((n && (!offsets || !values || (!data && offsets[n]))) || (elem_cap && !elems)) return RR_API_EINVAL;
+    if (flags & ~(RR_CTX_NO_SMALL | RR_CTX_ZL_RAW)) return RR_API_EINVAL;
     uint64_t base = 0, bad = 0, payload = 0;
     rr_elem *scratch = NULL;
     uint64_t scratch_cap = 0;
@@ -639,7 +654,7 @@ int rr_host_decode_batch(const uint8_t *data, const uint64_t *offsets, uint64_t 
         const uint64_t o = offsets[i], len = offsets[i + 1] - o;
         const uint8_t *b = data + o;
         rr_value *v = &values[i];
-        const uint64_t r = rr_host_reserve(b, len);
+        const uint64_t r = reserve_fl(b, len, flags);
         const int fits = base + r <= elem_cap;
         emit_t E = {b, o, fits ? elems + base : scratch, r, 0};
         if (!fits && r > scratch_cap) {   /* a capacity cut still needs the value's own verdict */
@@ -649,7 +664,7 @@ int rr_host_decode_batch(const uint8_t *data, const uint64_t *offsets, uint64_t 
             E.el = scratch;
         }
         uint64_t slots, pay;
-        int st = decode_one(&E, len, v, &slots, &pay);
+        int st = decode_one(&E, len, v, &slots, &pay, flags);
         if (st == RR_OK && slots != r) st = RR_E_COUNT;
         if (st != RR_OK) {
             v->n_elems = 0;
@@ -674,6 +689,11 @@ int rr_host_decode_batch(const uint8_t *data, const uint64_t *offsets, uint64_t 
         totals->payload = payload;
     }
     return RR_API_OK;
+}
+
+int rr_host_decode_batch(const uint8_t *data, const uint64_t *offsets, uint64_t n, rr_value *values, rr_elem *elems,
+                         uint64_t elem_cap, uint8_t *arena, rr_totals *totals) {
+    return rr_host_decode_batch_ex(data, offsets, n, values, elems, elem_cap, arena, totals, 0);
 }
 
 /* ---------------------------------------------------------------- encode */

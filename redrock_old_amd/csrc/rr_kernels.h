@@ -22,11 +22,12 @@ extern "C" {
  * decode_kernel's one-launch form alone, which keeps its look-back and end words there and leaves
  * them zero); zero / nzero: words the call zeroes on the way (the other half of the context's
  * double buffer).  first_only (test hooks): 1 launch only count_kernel (the two-launch form);
- * 2 the one-launch form sums every earlier window itself (its look-back's help path). */
+ * 2 the one-launch form sums every earlier window itself (its look-back's help path).
+ * flags: RR_CTX_ZL_RAW (rr_serdes.h), a kernel argument of every decode kernel. */
 hipError_t rr_launch_decode(const uint8_t *blob, const uint64_t *offsets, uint64_t n, rr_value *values,
                             rr_elem *elems, uint64_t elem_cap, uint8_t *arena, uint64_t *scratch, uint64_t *sums,
                             uint64_t *zero, uint64_t nzero, uint64_t data_cap, rr_totals *totals, hipStream_t stream,
-                            int first_only);
+                            int first_only, unsigned flags);
 uint64_t rr_decode_sums_words(uint64_t data_cap);
 hipError_t rr_launch_zero_words(uint64_t *words, uint64_t n, hipStream_t stream);
 hipError_t rr_launch_encode(const rr_value *values, const rr_elem *elems, uint64_t elem_cap, const uint8_t *arena,
@@ -60,7 +61,7 @@ int rr_small_decode_fits(uint64_t n, uint64_t data_cap);
 int rr_small_encode_fits(uint64_t n, uint64_t data_cap);
 hipError_t rr_launch_decode_small(const uint8_t *blob, const uint64_t *offsets, uint64_t n, rr_value *values,
                                   rr_elem *elems, uint64_t elem_cap, uint8_t *arena, uint64_t data_cap, rr_totals *totals,
-                                  uint32_t *done, uint32_t seq, hipStream_t stream);
+                                  uint32_t *done, uint32_t seq, unsigned flags, hipStream_t stream);
 hipError_t rr_launch_encode_small(const rr_value *values, const rr_elem *elems, uint64_t elem_cap, const uint8_t *arena,
                                   uint64_t arena_cap, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *offsets,
                                   rr_totals *totals, uint32_t *done, uint32_t seq, hipStream_t stream);

@@ -137,8 +137,10 @@ __device__ __forceinline__ uint32_t parse_ziplist(P zl, uint64_t L, uint64_t zof
 }
 
 // desObject rock_serdes.c:538-564 and des* :133-508, on one blob at b (batch offset off).
+// zraw (RR_CTX_ZL_RAW, uniform): a ziplist whose byte count equals the rest of the blob is
+// accepted unread, as its ZLRAW alone (desHash / desZset, :356-366, :455-466).
 template <bool EMIT, typename P>
-__device__ __forceinline__ Parsed parse_value(P b, uint64_t off, uint64_t len, rr_elem *out) {
+__device__ __forceinline__ Parsed parse_value(P b, uint64_t off, uint64_t len, rr_elem *out, uint32_t zraw) {
     Parsed r{RR_OK, 0, 0, 0, false};
     uint64_t n = 0, pay = 0;
     if (len < 5) { r.status = RR_E_SHORT; return r; }
@@ -231,6 +233,12 @@ __device__ __forceinline__ Parsed parse_value(P b, uint64_t off, uint64_t len, r
             p += 8;
             rem -= 8;
             if (rem != L) { st = RR_E_ZL_LEN; break; }
+            if (zraw && L <= 0xFFFFFFFFull) {   // (a count past rr_elem.len keeps the walk's verdict)
+                if (EMIT) put_elem(out, off + p, (uint32_t)L, RR_K_ZLRAW, 0);
+                n = 1;
+                pay = L;
+                break;
+            }
             uint64_t cnt;
             st = parse_ziplist<EMIT, P>(b + p, L, off + p, out + 1, cnt);
             if (st == RR_OK && (cnt & 1)) st = RR_E_ZL_CORRUPT;
@@ -421,9 +429,12 @@ __device__ __forceinline__ uint32_t list_count_lds(uint32_t b, uint32_t L) {   /
 }
 // The descriptor reservation (rr_format.h) and the walk class of a value from its header dwords
 // (b: the value's bytes, in global memory or an LDS stage).  LIST_LATER: a List's count is left
-// to the caller (count_kernel walks it from LDS), r = 0.
+// to the caller (count_kernel walks it from LDS), r = 0.  zraw (RR_CTX_ZL_RAW, uniform): a
+// ziplist whose byte count equals the rest of the blob owns one slot and joins the String class,
+// whose batch stores its ZLRAW from the header alone (do_string): no count walk, no C_ZL.
 template <bool LIST_LATER = false, typename P>
-__device__ __forceinline__ void reserve_classify(P b, uint64_t L, const uint32_t (&d)[6], uint64_t &r, uint32_t &c) {
+__device__ __forceinline__ void reserve_classify(P b, uint64_t L, const uint32_t (&d)[6], uint64_t &r, uint32_t &c,
+                                                 uint32_t zraw) {
     r = 0;
     c = C_EXACT;
     if (L < 5) return;
@@ -465,6 +476,7 @@ __device__ __forceinline__ void reserve_classify(P b, uint64_t L, const uint32_t
         case RR_TYPE_HASH_ZIPLIST:
         case RR_TYPE_ZSET_ZIPLIST: {
             const uint64_t Lz = u5;
+            if (zraw && Lz == L - 13 && f9 == 0) { r = 1; c = C_STR; return; }   // (f9: Lz < 2^32)
             c = (L >= 24 && Lz == L - 13 && f13 == Lz) ? C_ZL : C_EXACT;
             if (Lz != L - 13 || Lz < 11) return;
             const uint64_t zllen = (d[5] >> 8) & 0xFFFF;
@@ -533,7 +545,8 @@ __global__ __launch_bounds__(CNT_NT) void count_kernel(const uint8_t *__restrict
                                                        uint32_t nwin, uint32_t win,
                                                        uint32_t *__restrict__ counts, uint8_t *__restrict__ cls,
                                                        uint64_t *wtot, uint64_t *gtot,
-                                                       uint64_t *zero_words, uint64_t nzero, rr_totals *tot) {
+                                                       uint64_t *zero_words, uint64_t nzero, rr_totals *tot,
+                                                       uint32_t zraw) {
     __shared__ uint64_t lw[CNT_LW], lg[CNT_LG];
     __shared__ __attribute__((aligned(16))) uint8_t lstage[CNT_NT / RR_WAVE][CNT_LB];
     if (blockIdx.x == 0 && tot && threadIdx.x < 4) reinterpret_cast<uint64_t *>(tot)[threadIdx.x] = 0;
@@ -576,7 +589,7 @@ __global__ __launch_bounds__(CNT_NT) void count_kernel(const uint8_t *__restrict
     uint32_t w = 0xFFFFFFFFu;   // (lanes past n: a window no value has)
     uint32_t c = C_N;
     if (i < n) {
-        reserve_classify<true>(blob + o_hi, b1 - o_hi, d, r, c);
+        reserve_classify<true>(blob + o_hi, b1 - o_hi, d, r, c, zraw);
         cls[i] = (uint8_t)c;
         w = (uint32_t)dw(o_hi);
     }
@@ -719,11 +732,11 @@ __device__ __forceinline__ uint32_t mark_fixup(uint32_t *nfix) {
 template <typename P>
 __device__ __forceinline__ Acc exact_value(P src, uint64_t src0, uint64_t v, const uint64_t *__restrict__ offsets,
                                            uint64_t eb, uint64_t r, rr_value *__restrict__ values,
-                                           rr_elem *__restrict__ elems, uint64_t cap, uint32_t *nfix) {
+                                           rr_elem *__restrict__ elems, uint64_t cap, uint32_t *nfix, uint32_t zraw) {
     uint64_t pay = 0;
     const uint64_t o_lo = offsets[v], o_hi = offsets[v + 1];
     const P b = src + (o_lo - src0);
-    Parsed pr = parse_value<false, P>(b, o_lo, o_hi - o_lo, nullptr);
+    Parsed pr = parse_value<false, P>(b, o_lo, o_hi - o_lo, nullptr, zraw);
     uint32_t status = pr.status;
     uint64_t ne = pr.n;
     if (status == RR_OK && ne != r) status = RR_E_COUNT;
@@ -735,7 +748,7 @@ __device__ __forceinline__ Acc exact_value(P src, uint64_t src0, uint64_t v, con
     } else if (!fits) {
         status = RR_E_CAPACITY;
     } else {
-        Parsed e = parse_value<true, P>(b, o_lo, o_hi - o_lo, elems + eb);
+        Parsed e = parse_value<true, P>(b, o_lo, o_hi - o_lo, elems + eb, zraw);
         pay += e.payload;
         const uint32_t t = ld_u8(b);
         const uint64_t keys = t == RR_TYPE_HASH_HT ? ne / 2 : ne;
@@ -785,7 +798,7 @@ __device__ __forceinline__ Acc run_batch(const Src &src, uint32_t c, bool active
                                          uint64_t B, rsrc_t E, uint64_t eb0, const uint8_t *__restrict__ blob,
                                          const uint64_t *__restrict__ offsets, uint64_t eb_v, uint64_t r_v,
                                          rr_value *__restrict__ values, rr_elem *__restrict__ elems, uint64_t cap,
-                                         uint32_t *nfix) {
+                                         uint32_t *nfix, uint32_t zraw) {
     // (one exact_value call site: the parser is large and every inlined copy costs I-cache)
     bool exact = c == C_EXACT;
     Acc acc{0, 0};
@@ -811,7 +824,7 @@ __device__ __forceinline__ Acc run_batch(const Src &src, uint32_t c, bool active
         bool fail = false, fixup = false;
         if (c == C_STR) {
             if (active) do_string(H, l, vp);
-            enc = H.b5();
+            enc = H.type() == RR_TYPE_STRING ? H.b5() : 0u;   // (a raw-mode ziplist: RR_CTX_ZL_RAW)
         } else if (c == C_IS) {
             do_intset_g(src, H, l, active, G, g);
             ne = H.f9();
@@ -843,7 +856,7 @@ __device__ __forceinline__ Acc run_batch(const Src &src, uint32_t c, bool active
         }
         active &= g == 0;   // the exact parser runs once per value, on the group's lane 0
     }
-    if (active && exact) acc = exact_value(blob, 0, v, offsets, eb_v, r_v, values, elems, cap, nfix);
+    if (active && exact) acc = exact_value(blob, 0, v, offsets, eb_v, r_v, values, elems, cap, nfix, zraw);
     return acc;
 }
 
@@ -1120,6 +1133,8 @@ constexpr uint32_t DEC_KE = 2;
 // Two 512-thread workgroups per CU = 4 waves per SIMD, so at most 128 VGPRs: the allocator is
 // told so (left to itself it takes 137 for the hash-table walk and the CU holds one workgroup).
 constexpr int DEC_WPE = 4;
+// decode_kernel's option word (one kernel argument: no new instantiation for a mode)
+constexpr uint32_t DEC_HELP_ALL = 1, DEC_ZL_RAW = 2;
 
 // The one-launch decode's words in the context's sums (zero on entry, zero again when the call's
 // last window is done): [6] a wait that never ended (the error word), then per window its
@@ -1216,7 +1231,7 @@ __device__ __forceinline__ uint64_t wave_lower_bound(const uint64_t *__restrict_
 // memory: the look-back's help for a window that has not started (its workgroup not yet
 // dispatched), so that a window never waits on one that is not running.
 __device__ uint64_t one_window_sum(const uint8_t *__restrict__ blob, const uint64_t *__restrict__ offsets, uint64_t n,
-                                   uint32_t win, uint32_t p) {
+                                   uint32_t win, uint32_t p, uint32_t zraw) {
     const uint64_t v0 = wave_lower_bound(offsets, n, (uint64_t)p * win);
     const uint64_t v1 = wave_lower_bound(offsets, n, (uint64_t)(p + 1) * win);
     uint64_t sum = 0;
@@ -1225,7 +1240,7 @@ __device__ uint64_t one_window_sum(const uint8_t *__restrict__ blob, const uint6
         uint32_t d[6], c;
         uint64_t r;
         head24(blob, o, o1, d);
-        reserve_classify(blob + o, o1 - o, d, r, c);
+        reserve_classify(blob + o, o1 - o, d, r, c, zraw);
         sum += r;
     }
     return wave_sum(sum);
@@ -1261,7 +1276,9 @@ __global__ __launch_bounds__(NW * RR_WAVE) __attribute__((amdgpu_waves_per_eu(DE
     const uint32_t *__restrict__ first_val, const uint64_t *__restrict__ first_off, uint8_t *__restrict__ cls, uint32_t *__restrict__ counts,
     const uint64_t *wtot, const uint64_t *gtot, rr_value *__restrict__ values,
     rr_elem *__restrict__ elems, uint64_t elem_cap, uint8_t *__restrict__ arena, uint32_t nwin, uint32_t win,
-    rr_totals *tot, uint64_t *one, uint64_t *zero_words, uint64_t nzero, uint32_t help_all) {
+    rr_totals *tot, uint64_t *one, uint64_t *zero_words, uint64_t nzero, uint32_t opts) {
+    // opts: DEC_HELP_ALL (the test hook's forced help, ONE) | DEC_ZL_RAW (RR_CTX_ZL_RAW)
+    const uint32_t help_all = opts & DEC_HELP_ALL, zraw = opts & DEC_ZL_RAW;
     constexpr uint32_t NT = NW * RR_WAVE, STAGE = W + SLACK;
     static_assert(PMAX == NT, "a chunk is one value per thread (the slot scan)");
     static_assert(W % 16 == 0 && SLACK % 16 == 0, "tile shape");
@@ -1375,6 +1392,22 @@ __global__ __launch_bounds__(NW * RR_WAVE) __attribute__((amdgpu_waves_per_eu(DE
     // memory)
     constexpr uint32_t KT = (SLACK / 16 + NT - 1) / NT;
     const uint64_t ov_t0 = ov_w1 > ov_a ? ov_w1 : ov_a;
+    // RR_CTX_ZL_RAW: a window that would miss the stage only because its LAST value runs on (the
+    // one value that can pass the window's end) still takes it when that value is a ziplist the
+    // mode keeps raw — the classifier's rule, read from its header here: the String class reads
+    // 24 bytes of it and nothing else does, so the stage ends 32 bytes into it.  (A uniform branch
+    // no window takes with the flag off, and in raw mode only the windows that miss the stage.)
+    if (zraw && v_hi > v_lo && !(S1 - S0 <= STAGE && (S1 >> 4) <= ov_t0 + (uint64_t)KT * NT)) {
+        typedef uint64_t u64_ua __attribute__((aligned(1)));
+        const uint64_t ol = offsets[v_hi - 1], Ll = f_hi - ol;
+        if (Ll >= 13 + 32) {
+            const uint32_t t = blob[ol];
+            const uint64_t lz = *reinterpret_cast<const u64_ua *>(blob + ol + 5);
+            const uint64_t cut = (ol + 32 + 15) & ~15ull;
+            if ((t == RR_TYPE_HASH_ZIPLIST || t == RR_TYPE_ZSET_ZIPLIST) && lz == Ll - 13 && lz <= 0xFFFFFFFFull && cut < S1)
+                S1 = cut;
+        }
+    }
     const bool staged = S1 - S0 <= STAGE && (S1 >> 4) <= ov_t0 + (uint64_t)KT * NT;
     const uint64_t cap = elem_cap < 0xFFFFFFFFull ? elem_cap : 0xFFFFFFFFull;   // elem_base is 32-bit
     // (ONE: the first chunk's offsets, from the search's first samples when they hold them)
@@ -1443,10 +1476,10 @@ __global__ __launch_bounds__(NW * RR_WAVE) __attribute__((amdgpu_waves_per_eu(DE
         if (staged) {
             const uint32_t q = (uint32_t)(o - S0);
             lsrc.get<6>(q, d);   // (reads up to 28 bytes past q: inside the stage's slack)
-            reserve_classify(lsrc.S + q, o1 - o, d, r, c);
+            reserve_classify(lsrc.S + q, o1 - o, d, r, c, zraw);
         } else {
             head24(blob, o, o1, d);
-            reserve_classify(blob + o, o1 - o, d, r, c);
+            reserve_classify(blob + o, o1 - o, d, r, c, zraw);
         }
     };
 
@@ -1590,7 +1623,7 @@ __global__ __launch_bounds__(NW * RR_WAVE) __attribute__((amdgpu_waves_per_eu(DE
                     for (uint32_t w = 0; w < NW; ++w)
                         for (uint64_t m = lbw[b][1][w]; m; m &= m - 1) {
                             const uint32_t q = w * RR_WAVE + (uint32_t)__builtin_ctzll(m);
-                            const uint64_t sq = one_window_sum(blob, offsets, n, win, q);
+                            const uint64_t sq = one_window_sum(blob, offsets, n, win, q, zraw);
                             if (lane == 0) lb_store(&state[q], ONE_AGG | sq);
                         }
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (visible before the next round)
@@ -1674,9 +1707,9 @@ __global__ __launch_bounds__(NW * RR_WAVE) __attribute__((amdgpu_waves_per_eu(DE
                 if (lane == 0) atomicAdd((unsigned long long *)&prb[36], (unsigned long long)tof);
             })
             const Acc a = staged ? run_batch(lsrc, c, active, v, G, g, S0, E, eb_c, blob, offsets, eb_v, r_v, values,
-                                             elems, cap, &nfix)
+                                             elems, cap, &nfix, zraw)
                                  : run_batch(gsrc, c, active, v, G, g, S0, E, eb_c, blob, offsets, eb_v, r_v, values,
-                                             elems, cap, &nfix);
+                                             elems, cap, &nfix, zraw);
             bad += a.bad;
             pay += a.pay;
             PROBE(if (lane == 0) {
@@ -1818,7 +1851,8 @@ __global__ __launch_bounds__(SMALL_NT) void decode_small_kernel(const uint8_t *_
                                                                 rr_value *__restrict__ values,
                                                                 rr_elem *__restrict__ elems, uint64_t elem_cap,
                                                                 uint8_t *__restrict__ arena, uint64_t data_cap,
-                                                                rr_totals *tot, uint32_t *done, uint32_t seq) {
+                                                                rr_totals *tot, uint32_t *done, uint32_t seq,
+                                                                uint32_t zraw) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[SMALL_STAGE];
     __shared__ uint64_t wsum[SMALL_NT / RR_WAVE], red[2][SMALL_NT / RR_WAVE];
     __shared__ uint32_t nfix;
@@ -1873,7 +1907,7 @@ __global__ __launch_bounds__(SMALL_NT) void decode_small_kernel(const uint8_t *_
             const uint32_t q = (uint32_t)(o[j] - B0);
             uint32_t d[6];
             LdsSrc{S}.get<6>(q, d);   // (reads up to 28 bytes past q: inside the stage's slack)
-            reserve_classify(S + q, o[j + 1] - o[j], d, r[j], cl[j]);
+            reserve_classify(S + q, o[j + 1] - o[j], d, r[j], cl[j], zraw);
         }
         sum += r[j];
     }
@@ -1900,7 +1934,7 @@ __global__ __launch_bounds__(SMALL_NT) void decode_small_kernel(const uint8_t *_
             const uint64_t ev = s_eb[v], rv = s_r[v];
             Acc a{0, 0};
             if (c == C_EXACT) {
-                if (lane == 0) a = exact_value(S, B0, v, s_off, ev, rv, values, elems, cap, &nfix);
+                if (lane == 0) a = exact_value(S, B0, v, s_off, ev, rv, values, elems, cap, &nfix, zraw);
             } else {
                 const bool grouped = c == C_LIST || c == C_SL || c == C_IS || c == C_ZL;
                 const bool htg = (c == C_HT || c == C_HH) && GMAX >= ht_group_min(c == C_HH);
@@ -1908,7 +1942,7 @@ __global__ __launch_bounds__(SMALL_NT) void decode_small_kernel(const uint8_t *_
                 const rsrc_t E = make_rsrc(reinterpret_cast<const uint8_t *>(elems + ev),
                                            ev < cap ? (uint32_t)((cap - ev < rv ? cap - ev : rv) * 16) : 0u);
                 a = run_batch(lsrc, c, lane < G, v, G, lane & (G - 1), B0, E, ev, blob, s_off, ev, rv, values, elems, cap,
-                              &nfix);
+                              &nfix, zraw);
             }
             bad += a.bad;
             pay += a.pay;
@@ -1918,7 +1952,7 @@ __global__ __launch_bounds__(SMALL_NT) void decode_small_kernel(const uint8_t *_
 #pragma unroll 1
         for (uint32_t j = 0; j < SMALL_VPT; ++j) {
             if (v0 + j < n) {
-                const Acc a = exact_value(S, B0, v0 + j, offsets, eb, r[j], values, elems, cap, &nfix);
+                const Acc a = exact_value(S, B0, v0 + j, offsets, eb, r[j], values, elems, cap, &nfix, zraw);
                 bad += a.bad;
                 pay += a.pay;
             }
@@ -3251,9 +3285,10 @@ extern "C" int rr_small_decode_fits(uint64_t n, uint64_t data_cap) {
 }
 extern "C" hipError_t rr_launch_decode_small(const uint8_t *blob, const uint64_t *offsets, uint64_t n, rr_value *values,
                                              rr_elem *elems, uint64_t elem_cap, uint8_t *arena, uint64_t data_cap,
-                                             rr_totals *totals, uint32_t *done, uint32_t seq, hipStream_t stream) {
+                                             rr_totals *totals, uint32_t *done, uint32_t seq, unsigned flags,
+                                             hipStream_t stream) {
     hipLaunchKernelGGL(decode_small_kernel, dim3(1), dim3(SMALL_NT), 0, stream, blob, offsets, n, values, elems, elem_cap,
-                       arena, data_cap, totals, done, seq);
+                       arena, data_cap, totals, done, seq, (uint32_t)(flags & RR_CTX_ZL_RAW));
     return hipGetLastError();
 }
 
@@ -3415,7 +3450,8 @@ extern "C" uint64_t rr_decode_sums_words(uint64_t data_cap) {
 extern "C" hipError_t rr_launch_decode(const uint8_t *blob, const uint64_t *offsets, uint64_t n, rr_value *values,
                                        rr_elem *elems, uint64_t elem_cap, uint8_t *arena, uint64_t *scratch,
                                        uint64_t *sums, uint64_t *zero, uint64_t nzero, uint64_t data_cap,
-                                       rr_totals *totals, hipStream_t stream, int first_only) {
+                                       rr_totals *totals, hipStream_t stream, int first_only, unsigned flags) {
+    const uint32_t zraw = flags & RR_CTX_ZL_RAW ? DEC_ZL_RAW : 0u;
     uint32_t win = dec_win(data_cap), nw = (uint32_t)(data_cap / win + 1);
     // A small batch that fits one window per CU, at most a sort chunk (512 values) a window, gets
     // one window per CU instead of two: config 1 at 100K values 22.0 -> 19.1 us, config 2 / 4 at
@@ -3443,19 +3479,19 @@ extern "C" hipError_t rr_launch_decode(const uint8_t *blob, const uint64_t *offs
     if (first_only != 1 && nw <= dec_slots() && nw <= DEC_NW * RR_WAVE && dec_one()) {   // (a look-back thread per earlier window)
         hipLaunchKernelGGL((DECODE_ONE), dim3(nw), dim3(DEC_NW * RR_WAVE), 0, stream, blob, data_cap, offsets, n,
                            nullptr, nullptr, cls, counts, nullptr, nullptr, values, elems, elem_cap, arena, nw, win,
-                           totals, sums, zero, nzero, (uint32_t)(first_only == 2));
+                           totals, sums, zero, nzero, (first_only == 2 ? DEC_HELP_ALL : 0u) | zraw);
         return hipGetLastError();
     }
     if (data_cap < (1ull << 32))
         hipLaunchKernelGGL(count_kernel<true>, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, stream, blob, offsets, n,
-                           first_val, first_off, nw, win, counts, cls, wtot, gtot, zero, nzero, totals);
+                           first_val, first_off, nw, win, counts, cls, wtot, gtot, zero, nzero, totals, zraw);
     else
         hipLaunchKernelGGL(count_kernel<false>, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, stream, blob, offsets,
-                           n, first_val, first_off, nw, win, counts, cls, wtot, gtot, zero, nzero, totals);
+                           n, first_val, first_off, nw, win, counts, cls, wtot, gtot, zero, nzero, totals, zraw);
     if (first_only == 1) return hipGetLastError();
     hipLaunchKernelGGL((DECODE_KERNEL), dim3(nw), dim3(DEC_NW * RR_WAVE), 0, stream, blob, data_cap, offsets, n,
                        first_val, first_off, cls, counts, wtot, gtot, values, elems, elem_cap, arena, nw, win, totals,
-                       nullptr, nullptr, 0, 0u);
+                       nullptr, nullptr, 0, zraw);
     return hipGetLastError();
 }
 

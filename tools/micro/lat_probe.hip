@@ -98,7 +98,7 @@ int main() {
     CK(hipMemcpy(doff, o, 16, hipMemcpyHostToDevice));
     for (int i = 0; i < K; ++i) {
         const double t0 = now_us();
-        CK(rr_launch_decode_small(dblob, doff, 1, dval, del, 4096, NULL, (len + 15) & ~15ull, dtot, NULL, 0, s));
+        CK(rr_launch_decode_small(dblob, doff, 1, dval, del, 4096, NULL, (len + 15) & ~15ull, dtot, NULL, 0, 0, s));
         CK(hipStreamSynchronize(s));
         t[i] = now_us() - t0;
     }
@@ -109,7 +109,7 @@ int main() {
     // kernel time alone (events)
     for (int i = 0; i < K; ++i) {
         CK(hipEventRecord(e0, s));
-        CK(rr_launch_decode_small(dblob, doff, 1, dval, del, 4096, NULL, (len + 15) & ~15ull, dtot, NULL, 0, s));
+        CK(rr_launch_decode_small(dblob, doff, 1, dval, del, 4096, NULL, (len + 15) & ~15ull, dtot, NULL, 0, 0, s));
         CK(hipEventRecord(e1, s));
         CK(hipEventSynchronize(e1));
         float ms;
@@ -147,7 +147,7 @@ int main() {
             CK(hipMemcpy(doff, oo, 16, hipMemcpyHostToDevice));
             for (int i = 0; i < 200; ++i) {
                 CK(hipEventRecord(e0, s));
-                CK(rr_launch_decode_small(dblob, doff, 1, dval, del, 4096, NULL, (l + 15) & ~15ull, dtot, NULL, 0, s));
+                CK(rr_launch_decode_small(dblob, doff, 1, dval, del, 4096, NULL, (l + 15) & ~15ull, dtot, NULL, 0, 0, s));
                 CK(hipEventRecord(e1, s));
                 CK(hipEventSynchronize(e1));
                 float ms;
@@ -162,7 +162,7 @@ int main() {
     CK(hipMemcpy(doff, o, 16, hipMemcpyHostToDevice));
     // 4c. the one-launch encode kernel of the same value (its flat form from the decode above),
     //     device buffers, HIP events; and a host-mapped completion word instead (launch + spin)
-    CK(rr_launch_decode_small(dblob, doff, 1, dval, del, 4096, NULL, (len + 15) & ~15ull, dtot, NULL, 0, s));
+    CK(rr_launch_decode_small(dblob, doff, 1, dval, del, 4096, NULL, (len + 15) & ~15ull, dtot, NULL, 0, 0, s));
     CK(hipStreamSynchronize(s));
     rr_totals dt;
     CK(hipMemcpy(&dt, dtot, sizeof dt, hipMemcpyDeviceToHost));
@@ -192,7 +192,7 @@ int main() {
     for (int i = 0; i < K; ++i) {
         const uint32_t seq = (uint32_t)(2 * K + i) + 1;
         const double t0 = now_us();
-        CK(rr_launch_decode_small(dblob, doff, 1, dval, del, 4096, NULL, (len + 15) & ~15ull, dtot, df, seq, s));
+        CK(rr_launch_decode_small(dblob, doff, 1, dval, del, 4096, NULL, (len + 15) & ~15ull, dtot, df, seq, 0, s));
         while (*(volatile uint32_t *)hf != seq) {}
         t[i] = now_us() - t0;
     }

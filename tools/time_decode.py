@@ -1,5 +1,6 @@
 """Diagnostics: time rr_decode_batch (device-resident, HIP events) on a config batch.
-Usage: [RR_LIB=...] [RR_DECODE_MODE=k] python tools/time_decode.py [config] [n] [steps]"""
+Usage: [RR_LIB=...] [RR_DECODE_MODE=k] python tools/time_decode.py [--zl-raw] [config] [n] [steps]
+--zl-raw: the context keeps ziplists raw (RR_CTX_ZL_RAW; the default is the strict walk)."""
 import os
 import sys
 
@@ -10,14 +11,18 @@ import torch  # noqa: E402
 
 import redrock_old_amd as rr  # noqa: E402
 
-cfg = int(sys.argv[1]) if len(sys.argv) > 1 else 4
-n = int(sys.argv[2]) if len(sys.argv) > 2 else 1_000_000
-steps = int(sys.argv[3]) if len(sys.argv) > 3 else 10
+zl_raw = "--zl-raw" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a != "--zl-raw"]
+cfg = int(args[0]) if len(args) > 0 else 4
+n = int(args[1]) if len(args) > 1 else 1_000_000
+steps = int(args[2]) if len(args) > 2 else 10
 data, offs = rr.gen_batch(cfg, n)
 nb = int(offs[-1])
 dev = torch.device("cuda:0")
 eng = rr.Engine(0)
 eng.reserve(n, nb)
+if zl_raw:
+    eng.set_options(rr.CTX_ZL_RAW)
 d_data = torch.from_numpy(data).to(dev)
 d_offs = torch.from_numpy(offs.view(np.int64)).to(dev)
 cap = rr.elem_bound(n, nb)
@@ -37,4 +42,4 @@ e1.record(s)
 torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / steps
 print(f"cfg={cfg} n={n} bytes={nb} mode={os.environ.get('RR_DECODE_MODE', '0')} lib={os.environ.get('RR_LIB', 'librr_serdes.so')}"
-      f" ms={ms:.4f} GiB/s={nb / ms / 1e-3 / 2**30:.1f}")
+      f" zl={'raw' if zl_raw else 'strict'} ms={ms:.4f} GiB/s={nb / ms / 1e-3 / 2**30:.1f}")
