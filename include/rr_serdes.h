@@ -113,7 +113,13 @@ int rr_decode_batch(rr_ctx *ctx, const rr_blob_batch *in, rr_flat_batch *out,
  * size 0, counted in rr_totals.n_bad — when its status is not RR_OK, when its descriptors
  * [elem_base, elem_base + n_elems) pass in->elem_cap, when a payload it references passes
  * in->arena_cap, or when its descriptor kinds do not fit its type (RR_E_ENCODE rules,
- * rr_format.h).  Nothing outside [elems, elems + elem_cap) or [arena, arena + arena_cap) is read. */
+ * rr_format.h).  Nothing outside [elems, elems + elem_cap) or [arena, arena + arena_cap) is read.
+ * rr_totals.n_elems is the sum of every value's n_elems field, unencodable values included;
+ * rr_totals.payload counts the STR / ZLRAW bytes of the values written, none of an unencodable
+ * value or of one past data_cap.  Of a ziplist value only descriptor 0, the ZLRAW, is looked at
+ * and written: whatever descriptors follow it are ignored.  rr_elem.zenc and rr_elem.rsv are
+ * ignored, and so is rr_value.enc of every type but STRING and SET_INTSET.  rr_value.lru is
+ * written masked to 24 bits (RR_LRU_MASK).  tests/encode_expect.py states the whole rule. */
 int rr_encode_batch(rr_ctx *ctx, const rr_flat_batch *in, rr_blob_batch *out,
                     rr_totals *d_totals, void *stream);
 
