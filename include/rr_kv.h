@@ -14,7 +14,7 @@
  * The store is the caller's, through rr_kv_ops (RocksDB's MultiGet / WriteBatch in RedRock;
  * RocksDB is not part of this build).  With RR_KV_SNAPPY the stored values are snappy streams
  * (rr_snappy.h): store-side compression is then turned off (kNoCompression), since the value
- * arrives compressed.
+ * arrives compressed.  RR_KV_LZ4 is the same route with LZ4 streams (rr_lz4.h).
  */
 #ifndef RR_KV_H
 #define RR_KV_H
@@ -29,6 +29,7 @@ extern "C" {
 #endif
 
 #define RR_KV_SNAPPY 1   /* values are stored as snappy raw streams, (de)compressed on the GPU */
+#define RR_KV_LZ4    2   /* the same route with LZ4 streams (rr_lz4.h); both flags together: RR_API_EINVAL */
 
 typedef struct rr_kv_ops {
     void *user;

@@ -93,6 +93,9 @@ COMM_ID_BYTES = 128
 # include/rr_snappy.h (GPU block compression)
 SNAPPY_EXPORTS = ["rr_snappy_max_compressed_length", "rr_snappy_compress_bound", "rr_snappy_compress_batch",
                   "rr_snappy_decompress_batch", "rr_snappy_compress_batch_host", "rr_snappy_decompress_batch_host"]
+# include/rr_lz4.h (GPU LZ4 block compression beside snappy, row f3)
+LZ4_EXPORTS = ["rr_lz4_max_compressed_length", "rr_lz4_compress_bound", "rr_lz4_compress_batch",
+               "rr_lz4_decompress_batch", "rr_lz4_compress_batch_host", "rr_lz4_decompress_batch_host"]
 # include/rr_rdb.h (batched snapshot restore over the fork-child pipes, row f4; used from C)
 RDB_EXPORTS = ["rr_rdb_request_batch", "rr_rdb_blobs_free", "rr_rdb_request_flat", "rr_rdb_flat_free", "rr_rdb_serve"]
 # include/rr_kv.h (batched store I/O around the GPU path, row f2; used from C)
@@ -101,6 +104,7 @@ KV_EXPORTS = ["rr_kv_dump_batch", "rr_kv_restore_batch"]
 HOST_EXPORTS = ["rr_host_reserve", "rr_host_decode_value", "rr_host_check_value", "rr_host_decode_batch",
                 "rr_host_encode_size", "rr_host_encode_value", "rr_host_encode_batch"]
 SNAPPY_STATUS = {0: "OK", 1: "HEADER", 2: "TRUNC", 3: "OFFSET", 4: "OVERFLOW", 5: "LENGTH", 6: "CAPACITY"}
+LZ4_STATUS = dict(SNAPPY_STATUS)   # RR_LZ4_* parallel RR_SNAPPY_*
 
 _lib = None
 
@@ -168,6 +172,15 @@ def lib():
     L.rr_snappy_decompress_batch.argtypes = [vp, C.POINTER(BlobBatch), C.POINTER(BlobBatch), vp, vp]
     L.rr_snappy_compress_batch_host.argtypes = [vp, vp, vp, u64, vp, u64, vp]
     L.rr_snappy_decompress_batch_host.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp]
+    if "RR_LIB" not in os.environ or hasattr(L, "rr_lz4_compress_batch"):   # (RR_LIB: an older build may predate them)
+        L.rr_lz4_max_compressed_length.argtypes = [u64]
+        L.rr_lz4_max_compressed_length.restype = u64
+        L.rr_lz4_compress_bound.argtypes = [u64, u64]
+        L.rr_lz4_compress_bound.restype = u64
+        L.rr_lz4_compress_batch.argtypes = [vp, C.POINTER(BlobBatch), C.POINTER(BlobBatch), vp]
+        L.rr_lz4_decompress_batch.argtypes = [vp, C.POINTER(BlobBatch), C.POINTER(BlobBatch), vp, vp]
+        L.rr_lz4_compress_batch_host.argtypes = [vp, vp, vp, u64, vp, u64, vp]
+        L.rr_lz4_decompress_batch_host.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp]
     if hasattr(L, "rr_host_decode_batch"):   # (RR_LIB: an older build for A/B timing may predate it)
         L.rr_host_reserve.argtypes = [vp, u64]
         L.rr_host_reserve.restype = u64
@@ -513,6 +526,43 @@ class Engine:
         inb = BlobBatch(comp.data_ptr(), offsets.data_ptr(), n, comp.numel())
         outb = BlobBatch(out.data_ptr(), out_offsets.data_ptr(), n, out.numel())
         _check(self._L.rr_snappy_decompress_batch(self._ctx, C.byref(inb), C.byref(outb),
+                                                  C.c_void_p(status.data_ptr()), _sp(stream)))
+
+    # ---- LZ4 block compression (include/rr_lz4.h) -----------------------------------------
+    def lz4_compress_host(self, data: np.ndarray, offsets: np.ndarray):
+        """Blocks [offsets[i], offsets[i+1]) of data -> (packed compressed bytes, offsets)."""
+        data = np.ascontiguousarray(data, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n = len(offsets) - 1
+        cap = int(self._L.rr_lz4_compress_bound(n, int(offsets[-1])))
+        out = np.zeros(max(cap, 1), np.uint8)
+        oo = np.zeros(n + 1, np.uint64)
+        _check(self._L.rr_lz4_compress_batch_host(self._ctx, _ptr(data), _ptr(offsets), n, _ptr(out), cap, _ptr(oo)))
+        return out[:int(oo[-1])], oo
+
+    def lz4_decompress_host(self, comp: np.ndarray, offsets: np.ndarray, out_cap: int):
+        """(out bytes, out offsets, per-block status) of LZ4 blocks."""
+        comp = np.ascontiguousarray(comp, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n = len(offsets) - 1
+        out = np.zeros(max(out_cap, 1), np.uint8)
+        oo = np.zeros(n + 1, np.uint64)
+        st = np.zeros(max(n, 1), np.uint8)
+        _check(self._L.rr_lz4_decompress_batch_host(self._ctx, _ptr(comp), _ptr(offsets), n, _ptr(out), out_cap,
+                                                       _ptr(oo), _ptr(st)))
+        return out[:int(oo[-1])], oo, st[:n]
+
+    def lz4_compress_device(self, data, offsets, out, out_offsets, stream=None):
+        n = offsets.numel() - 1
+        inb = BlobBatch(data.data_ptr(), offsets.data_ptr(), n, data.numel())
+        outb = BlobBatch(out.data_ptr(), out_offsets.data_ptr(), n, out.numel())
+        _check(self._L.rr_lz4_compress_batch(self._ctx, C.byref(inb), C.byref(outb), _sp(stream)))
+
+    def lz4_decompress_device(self, comp, offsets, out, out_offsets, status, stream=None):
+        n = offsets.numel() - 1
+        inb = BlobBatch(comp.data_ptr(), offsets.data_ptr(), n, comp.numel())
+        outb = BlobBatch(out.data_ptr(), out_offsets.data_ptr(), n, out.numel())
+        _check(self._L.rr_lz4_decompress_batch(self._ctx, C.byref(inb), C.byref(outb),
                                                   C.c_void_p(status.data_ptr()), _sp(stream)))
 
     def encode_device(self, values, elems, arena, out_data, out_offsets, totals, stream=None):

@@ -43,6 +43,20 @@ hipError_t rr_launch_snappy_decompress(const uint8_t *in, uint64_t in_cap, const
                                        hipStream_t stream);
 hipError_t rr_launch_snappy_compress(const uint8_t *in, uint64_t in_cap, const uint64_t *in_offs, uint64_t n, uint8_t *out,
                                      uint64_t *out_offs, uint64_t *scratch, uint64_t slot_bytes, hipStream_t stream);
+/* shared by the snappy and LZ4 codecs (rr_snappy.hip): the varint32 length preambles of n blocks
+ * (out_offs[i] the announced length, out_offs[n] = 0, status[i] 0 or 1 = E_HEADER, lb[0, lbw)
+ * zeroed for the scan that follows), and the per-block slots -> packed output copy */
+hipError_t rr_launch_varint_lengths(const uint8_t *in, const uint64_t *in_offs, uint64_t n, uint64_t *out_offs,
+                                    uint8_t *status, uint64_t *lb, uint64_t lbw, hipStream_t stream);
+hipError_t rr_launch_slot_pack(const uint8_t *slots, const uint64_t *slot_offs, uint64_t n, uint8_t *out,
+                               const uint64_t *out_offs, hipStream_t stream);
+/* rr_lz4.hip (include/rr_lz4.h) */
+uint64_t rr_lz4_scratch_words(uint64_t n, uint64_t slot_bytes);
+hipError_t rr_launch_lz4_decompress(const uint8_t *in, uint64_t in_cap, const uint64_t *in_offs, uint64_t n, uint8_t *out,
+                                    uint64_t out_cap, uint64_t *out_offs, uint8_t *status, uint64_t *scratch,
+                                    hipStream_t stream);
+hipError_t rr_launch_lz4_compress(const uint8_t *in, uint64_t in_cap, const uint64_t *in_offs, uint64_t n, uint8_t *out,
+                                  uint64_t *out_offs, uint64_t *scratch, uint64_t slot_bytes, hipStream_t stream);
 hipError_t rr_launch_shard_plan(const uint64_t *offsets, uint64_t n, uint32_t g, uint64_t *plan, hipStream_t stream);
 hipError_t rr_launch_offsets_rebase(uint64_t *offs, uint64_t count, uint64_t sub, hipStream_t stream);
 hipError_t rr_launch_flat_rebase(rr_value *values, uint64_t n, rr_elem *elems, uint64_t ne, uint64_t elem_add,

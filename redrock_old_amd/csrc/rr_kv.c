@@ -1,7 +1,7 @@
 /*
  * rr_kv.c — batched store I/O around the GPU path (include/rr_kv.h):
  * one store call per batch, one upload and one download per batch, encode / decode and the
- * optional snappy step back to back on the device.
+ * optional snappy or LZ4 step back to back on the device.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -9,6 +9,7 @@
 #include "rr_internal.h"
 #include "../../include/rr_kv.h"
 #include "../../include/rr_snappy.h"
+#include "../../include/rr_lz4.h"
 
 #define fail rr_fail
 
@@ -41,6 +42,7 @@ int rr_kv_dump_batch(rr_ctx *c, const rr_kv_ops *kv, int dbi, size_t k, const ch
     if (!c || !kv || !kv->write_batch || (k && (!keys || !key_lens || !values)) || (n_elems && !elems) ||
         (arena_bytes && !arena))
         return fail(RR_API_EINVAL, "rr_kv_dump_batch: NULL argument");
+    if ((flags & RR_KV_SNAPPY) && (flags & RR_KV_LZ4)) return fail(RR_API_EINVAL, "rr_kv_dump_batch: RR_KV_SNAPPY and RR_KV_LZ4 together");
     if (k == 0) return RR_API_OK;
     dbufs d = {{0}, 0};
     int rc = RR_API_OK;
@@ -70,13 +72,14 @@ int rr_kv_dump_batch(rr_ctx *c, const rr_kv_ops *kv, int dbi, size_t k, const ch
     if (t.n_bad) { rc = fail(RR_API_EINVAL, "rr_kv_dump_batch: %llu values cannot be encoded", (unsigned long long)t.n_bad); goto out; }
     const uint8_t *src = dout;
     const uint64_t *soffs = doffs;
-    if (flags & RR_KV_SNAPPY) {
-        const uint64_t zcap = rr_snappy_compress_bound(k, cap);
+    if (flags & (RR_KV_SNAPPY | RR_KV_LZ4)) {
+        const int lz4 = (flags & RR_KV_LZ4) != 0;
+        const uint64_t zcap = lz4 ? rr_lz4_compress_bound(k, cap) : rr_snappy_compress_bound(k, cap);
         uint8_t *dz = dalloc(&d, zcap + 16);
         uint64_t *dzo = dalloc(&d, (k + 1) * sizeof(uint64_t));
         NEED(dz && dzo);
         rr_blob_batch z = {dz, dzo, k, zcap};
-        if ((rc = rr_snappy_compress_batch(c, &blobs, &z, s))) goto out;
+        if ((rc = lz4 ? rr_lz4_compress_batch(c, &blobs, &z, s) : rr_snappy_compress_batch(c, &blobs, &z, s))) goto out;
         src = dz;
         soffs = dzo;
     }
@@ -99,7 +102,8 @@ out:
     return rc;
 }
 
-/* varint32 length preamble of a snappy stream (snappy.cc:779-800); 0 on success */
+/* varint32 length preamble of a snappy stream (snappy.cc:779-800; an LZ4 stream's is read by
+ * the same rule, rr_lz4.h); 0 on success */
 static int snappy_len(const uint8_t *p, size_t n, uint64_t *len) {
     uint32_t v = 0, shift = 0;
     for (size_t i = 0; i < n && shift < 32; i++, shift += 7) {
@@ -115,6 +119,8 @@ int rr_kv_restore_batch(rr_ctx *c, const rr_kv_ops *kv, int dbi, size_t k, const
                         const size_t *key_lens, int flags, rr_rdb_flat *out) {
     if (!c || !kv || !kv->multi_get || !out || (k && (!keys || !key_lens))) return fail(RR_API_EINVAL, "rr_kv_restore_batch: NULL argument");
     memset(out, 0, sizeof *out);
+    if ((flags & RR_KV_SNAPPY) && (flags & RR_KV_LZ4)) return fail(RR_API_EINVAL, "rr_kv_restore_batch: RR_KV_SNAPPY and RR_KV_LZ4 together");
+    const int zip = (flags & (RR_KV_SNAPPY | RR_KV_LZ4)) != 0, lz4 = (flags & RR_KV_LZ4) != 0;
     if (k == 0) return RR_API_OK;
     dbufs d = {{0}, 0};
     int rc = RR_API_OK;
@@ -133,11 +139,11 @@ int rr_kv_restore_batch(rr_ctx *c, const rr_kv_ops *kv, int dbi, size_t k, const
     NEED(host = (uint8_t *)calloc(spad + 16, 1));
     for (size_t i = 0; i < k; i++) memcpy(host + soffs[i], vals[i], vlens[i]);
     uint64_t bbytes = sbytes;
-    if (flags & RR_KV_SNAPPY) {   /* the blob sizes come from the streams' preambles */
+    if (zip) {   /* the blob sizes come from the streams' preambles */
         bbytes = 0;
         for (size_t i = 0; i < k; i++) {
             uint64_t l;
-            if (snappy_len(host + soffs[i], vlens[i], &l)) { rc = fail(RR_API_EINVAL, "value %zu: bad snappy preamble", i); goto out; }
+            if (snappy_len(host + soffs[i], vlens[i], &l)) { rc = fail(RR_API_EINVAL, "value %zu: bad %s preamble", i, lz4 ? "lz4" : "snappy"); goto out; }
             bbytes += l;
         }
     }
@@ -149,13 +155,13 @@ int rr_kv_restore_batch(rr_ctx *c, const rr_kv_ops *kv, int dbi, size_t k, const
     CK(hipMemcpyAsync(ds, host, spad, hipMemcpyHostToDevice, s));
     CK(hipMemcpyAsync(dso, soffs, (k + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     rr_blob_batch blobs = {ds, dso, k, spad};
-    if (flags & RR_KV_SNAPPY) {
+    if (zip) {
         uint8_t *db = dalloc(&d, bpad + 16), *dst = dalloc(&d, k);
         uint64_t *dbo = dalloc(&d, (k + 1) * sizeof(uint64_t));
         NEED(db && dst && dbo);
         CK(hipMemsetAsync(db, 0, bpad + 16, s));   /* (the decode reads the padding as zeros) */
         rr_blob_batch z = {ds, dso, k, spad}, b = {db, dbo, k, bpad};
-        if ((rc = rr_snappy_decompress_batch(c, &z, &b, dst, s))) goto out;
+        if ((rc = lz4 ? rr_lz4_decompress_batch(c, &z, &b, dst, s) : rr_snappy_decompress_batch(c, &z, &b, dst, s))) goto out;
         uint8_t *hst = (uint8_t *)malloc(k);
         NEED(hst);
         hipError_t e = hipMemcpyAsync(hst, dst, k, hipMemcpyDeviceToHost, s);
@@ -166,7 +172,7 @@ int rr_kv_restore_batch(rr_ctx *c, const rr_kv_ops *kv, int dbi, size_t k, const
         const uint8_t code = bad < k ? hst[bad] : 0;
         free(hst);
         CK(e);
-        if (bad < k) { rc = fail(RR_API_EINVAL, "value %zu does not decompress (snappy status %u)", bad, code); goto out; }
+        if (bad < k) { rc = fail(RR_API_EINVAL, "value %zu does not decompress (%s status %u)", bad, lz4 ? "lz4" : "snappy", code); goto out; }
         blobs = b;
     }
     rr_value *dv = dalloc(&d, k * sizeof(rr_value));

@@ -1005,6 +1005,24 @@ extern "C" uint64_t rr_snappy_scratch_words(uint64_t n, uint64_t slot_bytes) {
     return rr_scan_words(n) + 1 + (n + 1) + (slot_bytes + 7) / 8 + 2;
 }
 
+// The two steps the LZ4 codec (rr_lz4.hip) shares with this one: the varint32 length preambles
+// (snz_len_kernel: out_offs[i] = the announced length, status[i] = OK / E_HEADER, out_offs[n] = 0,
+// lb[0, lbw) zeroed for the scan that follows) and the slots -> packed output copy.
+extern "C" hipError_t rr_launch_varint_lengths(const uint8_t *in, const uint64_t *in_offs, uint64_t n, uint64_t *out_offs,
+                                               uint8_t *status, uint64_t *lb, uint64_t lbw, hipStream_t stream) {
+    const uint64_t m = (n + 1 > lbw ? n + 1 : lbw);
+    hipLaunchKernelGGL(snz_len_kernel, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, stream, in, in_offs, n, out_offs,
+                       status, lb, (uint32_t)lbw);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rr_launch_slot_pack(const uint8_t *slots, const uint64_t *slot_offs, uint64_t n, uint8_t *out,
+                                          const uint64_t *out_offs, hipStream_t stream) {
+    hipLaunchKernelGGL(snz_pack_kernel, dim3(grid_for((n + PACK_WPB - 1) / PACK_WPB, 1u << 20)), dim3(PACK_WPB * WAVE), 0, stream, slots,
+                       slot_offs, n, out, out_offs);
+    return hipGetLastError();
+}
+
 // decompression: 3 launches (length preambles, scan, blocks)
 extern "C" hipError_t rr_launch_snappy_decompress(const uint8_t *in, uint64_t in_cap, const uint64_t *in_offs, uint64_t n, uint8_t *out,
                                                   uint64_t out_cap, uint64_t *out_offs, uint8_t *status,
