@@ -36,6 +36,11 @@ extern "C" {
 #endif
 
 #define RR_RDB_FLAT_TAG (-0x5244)   /* a dbi no RedRock database has: marks a FLAT request */
+/* SAVE: a request of the FLAT request's shape under this dbi; the service decodes the k blobs and
+ * saves them as RDB value payloads on its GPU (rr_rdbsave_batch, include/rr_rdbsave.h) and answers
+ * u64 n, u64 bytes, types[n], status[n], offsets[n + 1], data[bytes].  The child side is
+ * rr_rdbsave_request (rr_rdbsave.h); RAW and FLAT requests are unchanged. */
+#define RR_RDB_SAVE_TAG (-0x5245)
 
 /* blobs of one batch: data (16-byte aligned, zero-padded to 16) and offsets[n+1] (malloc'd) */
 typedef struct rr_rdb_blobs {

@@ -61,6 +61,10 @@ class FlatBatch(C.Structure):
                 ("elem_cap", C.c_uint64), ("arena_cap", C.c_uint64)]
 
 
+class RdbSaveOpts(C.Structure):
+    _fields_ = [("list_fill", C.c_int32), ("rsv", C.c_uint32)]
+
+
 class Shard(C.Structure):
     _fields_ = [("v0", C.c_uint64), ("v1", C.c_uint64), ("b0", C.c_uint64), ("b1", C.c_uint64)]
 
@@ -103,6 +107,10 @@ KV_EXPORTS = ["rr_kv_dump_batch", "rr_kv_restore_batch"]
 # include/rr_host.h (the host codec: RedRock's per-key call sites through the compat shim, row f1)
 HOST_EXPORTS = ["rr_host_reserve", "rr_host_decode_value", "rr_host_check_value", "rr_host_decode_batch",
                 "rr_host_encode_size", "rr_host_encode_value", "rr_host_encode_batch"]
+# include/rr_rdbsave.h (flat batch -> RDB value payloads for the snapshot child, row f4)
+RDBSAVE_EXPORTS = ["rr_rdbsave_bound", "rr_rdbsave_batch", "rr_rdbsave_batch_host", "rr_rdbsave_request",
+                   "rr_rdbsave_result_free"]
+E_CAPACITY, E_ENCODE = 11, 12   # the per-value statuses of rdbsave (RR_E_*, rr_format.h)
 SNAPPY_STATUS = {0: "OK", 1: "HEADER", 2: "TRUNC", 3: "OFFSET", 4: "OVERFLOW", 5: "LENGTH", 6: "CAPACITY"}
 LZ4_STATUS = dict(SNAPPY_STATUS)   # RR_LZ4_* parallel RR_SNAPPY_*
 
@@ -181,6 +189,12 @@ def lib():
         L.rr_lz4_decompress_batch.argtypes = [vp, C.POINTER(BlobBatch), C.POINTER(BlobBatch), vp, vp]
         L.rr_lz4_compress_batch_host.argtypes = [vp, vp, vp, u64, vp, u64, vp]
         L.rr_lz4_decompress_batch_host.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp]
+    if "RR_LIB" not in os.environ or hasattr(L, "rr_rdbsave_batch"):   # (RR_LIB: an older build may predate them)
+        L.rr_rdbsave_bound.argtypes = [u64, u64, u64]
+        L.rr_rdbsave_bound.restype = u64
+        L.rr_rdbsave_batch.argtypes = [vp, C.POINTER(FlatBatch), C.POINTER(BlobBatch), vp, vp, vp, C.POINTER(RdbSaveOpts), vp]
+        L.rr_rdbsave_batch_host.argtypes = [vp, vp, vp, u64, vp, u64, u64, C.POINTER(RdbSaveOpts), vp, u64, vp, vp, vp,
+                                            C.POINTER(Totals)]
     if hasattr(L, "rr_host_decode_batch"):   # (RR_LIB: an older build for A/B timing may predate it)
         L.rr_host_reserve.argtypes = [vp, u64]
         L.rr_host_reserve.restype = u64
@@ -565,6 +579,38 @@ class Engine:
         _check(self._L.rr_lz4_decompress_batch(self._ctx, C.byref(inb), C.byref(outb),
                                                   C.c_void_p(status.data_ptr()), _sp(stream)))
 
+    # ---- RDB value payloads (include/rr_rdbsave.h) -----------------------------------------
+    def rdbsave_host(self, values: np.ndarray, elems: np.ndarray, arena: np.ndarray, list_fill: int = -2,
+                     data_cap: int | None = None):
+        """Flat batch -> (types, data, offsets, status, totals): the bytes rdbSaveObject writes per value."""
+        n = len(values)
+        values = np.ascontiguousarray(values, VALUE_DT)
+        elems = np.ascontiguousarray(elems, ELEM_DT)
+        arena = np.ascontiguousarray(arena, np.uint8)
+        if data_cap is None:
+            data_cap = rdbsave_bound(values, elems)
+        data = np.zeros(max(data_cap, 1), np.uint8)
+        offsets = np.zeros(n + 1, np.uint64)
+        types = np.zeros(max(n, 1), np.uint8)
+        status = np.zeros(max(n, 1), np.uint8)
+        t = Totals()
+        opts = RdbSaveOpts(list_fill, 0)
+        _check(self._L.rr_rdbsave_batch_host(self._ctx, _ptr(values), _ptr(elems), len(elems), _ptr(arena), arena.size,
+                                             n, C.byref(opts), _ptr(data), data_cap, _ptr(offsets), _ptr(types),
+                                             _ptr(status), C.byref(t)))
+        return types[:n], data[:min(int(offsets[-1]), data_cap)], offsets, status[:n], t.as_dict()
+
+    def rdbsave_device(self, values, elems, arena, out_data, out_offsets, types, status, totals, list_fill: int = -2,
+                       stream=None):
+        """rr_rdbsave_batch on torch CUDA tensors (uint8 views of the flat records); no host sync."""
+        n = out_offsets.numel() - 1
+        inb = FlatBatch(values.data_ptr(), elems.data_ptr(), arena.data_ptr(), n, elems.numel() // 16, arena.numel())
+        outb = BlobBatch(out_data.data_ptr(), out_offsets.data_ptr(), n, out_data.numel())
+        opts = RdbSaveOpts(list_fill, 0)
+        _check(self._L.rr_rdbsave_batch(self._ctx, C.byref(inb), C.byref(outb), C.c_void_p(types.data_ptr()),
+                                        C.c_void_p(status.data_ptr()), C.c_void_p(totals.data_ptr()), C.byref(opts),
+                                        _sp(stream)))
+
     def encode_device(self, values, elems, arena, out_data, out_offsets, totals, stream=None):
         n = out_offsets.numel() - 1
         inb = FlatBatch(values.data_ptr(), elems.data_ptr(), arena.data_ptr(), n, elems.numel() // 16,
@@ -633,3 +679,9 @@ def encode_bound(values: np.ndarray, elems: np.ndarray) -> int:
     """Upper bound on encoded bytes for a flat batch (decimal ints <= 20 chars + 4-byte prefix;
     every other element costs <= 16 + len)."""
     return int(len(values) * 13 + len(elems) * 24 + int(elems["len"].astype(np.uint64).sum()) + 16)
+
+
+def rdbsave_bound(values: np.ndarray, elems: np.ndarray) -> int:
+    """rr_rdbsave_bound of a flat batch: an upper bound on the bytes rdbsave writes for it."""
+    pay = int(elems["len"][(elems["kind"] == K_STR) | (elems["kind"] == K_ZLRAW)].astype(np.uint64).sum())
+    return int(lib().rr_rdbsave_bound(len(values), len(elems), pay))

@@ -12,6 +12,7 @@
 
 #include "rr_internal.h"
 #include "../../include/rr_rdb.h"
+#include "../../include/rr_rdbsave.h"
 
 #define fail rr_fail
 
@@ -245,8 +246,30 @@ static void drop_vals(reqs_t *r, void (*free_val)(void *)) {
         if (r->vals[i] && free_val) free_val(r->vals[i]);
 }
 
+/* a SAVE request's answer from the decoded batch: u64 n, u64 bytes, types, status, offsets, data */
+static int answer_save(int fd_resp, rr_ctx *ctx, const rr_value *vals, const rr_elem *els, uint64_t n_elems,
+                       const uint8_t *arena, uint64_t bytes, uint64_t n) {
+    uint64_t pay = 0;
+    for (uint64_t i = 0; i < n_elems; i++)
+        if (els[i].kind == RR_K_STR || els[i].kind == RR_K_ZLRAW) pay += els[i].len;
+    const uint64_t cap = rr_rdbsave_bound(n, n_elems, pay);
+    uint8_t *out = (uint8_t *)malloc(cap + 16), *ts = (uint8_t *)malloc(2 * n + 1);
+    uint64_t *offs = (uint64_t *)malloc((n + 1) * sizeof(uint64_t));
+    int rc = -1;
+    rr_totals t;
+    if (out && ts && offs &&
+        rr_rdbsave_batch_host(ctx, vals, els, n_elems, arena, bytes, n, NULL, out, cap, offs, ts, ts + n, &t) == RR_API_OK) {
+        const uint64_t h[2] = {n, offs[n]};
+        rc = (write_full(fd_resp, h, sizeof h) == 1 && write_full(fd_resp, ts, 2 * n) == 1 &&
+              write_full(fd_resp, offs, (n + 1) * sizeof(uint64_t)) == 1 && write_full(fd_resp, out, offs[n]) == 1)
+                 ? 0 : -1;
+    }
+    free(out); free(ts); free(offs);
+    return rc;
+}
+
 static int serve_flat(int fd_req, int fd_resp, reqs_t *r, rr_rdb_multiget_fn get, void (*free_val)(void *), void *user,
-                      rr_ctx *ctx) {
+                      rr_ctx *ctx, int save) {
     size_t k;
     if (read_full(fd_req, &k, sizeof k) != 1) return -1;
     for (size_t i = 0; i < k; i++) {
@@ -267,7 +290,10 @@ static int serve_flat(int fd_req, int fd_resp, reqs_t *r, rr_rdb_multiget_fn get
     rr_totals t;
     if (data && arena && vals && els) {
         for (size_t i = 0; i < r->n; i++) memcpy(data + offs[i], r->vals[i], r->vlens[i]);
-        if (rr_decode_batch_host(ctx, data, offs, r->n, vals, els, cap, arena, &t) == RR_API_OK) {
+        const int dec = rr_decode_batch_host(ctx, data, offs, r->n, vals, els, cap, arena, &t);
+        if (dec == RR_API_OK && save) {
+            rc = answer_save(fd_resp, ctx, vals, els, t.n_elems < cap ? t.n_elems : cap, arena, bytes, r->n);
+        } else if (dec == RR_API_OK) {
             const uint64_t h[3] = {r->n, t.n_elems < cap ? t.n_elems : cap, bytes};
             rc = (write_full(fd_resp, h, sizeof h) == 1 && write_full(fd_resp, vals, h[0] * sizeof(rr_value)) == 1 &&
                   write_full(fd_resp, els, h[1] * sizeof(rr_elem)) == 1 && write_full(fd_resp, arena, bytes) == 1)
@@ -293,20 +319,23 @@ int rr_rdb_serve(int fd_req, int fd_resp, rr_rdb_multiget_fn get, void (*free_va
             if (g == 0) break;                              /* normal exit: the child closed the pipe */
             if (g < 0) { rc = fail(RR_API_EINVAL, "request read error"); break; }
         }
-        if (dbi == RR_RDB_FLAT_TAG) {
-            if (serve_flat(fd_req, fd_resp, &r, get, free_val, user, ctx)) { rc = fail(RR_API_EINVAL, "flat request failed"); break; }
+        if (dbi == RR_RDB_FLAT_TAG || dbi == RR_RDB_SAVE_TAG) {
+            if (serve_flat(fd_req, fd_resp, &r, get, free_val, user, ctx, dbi == RR_RDB_SAVE_TAG)) {
+                rc = fail(RR_API_EINVAL, dbi == RR_RDB_SAVE_TAG ? "save request failed" : "flat request failed");
+                break;
+            }
             reqs_clear(&r);
             continue;
         }
         if (read_key(fd_req, dbi, &r)) { rc = fail(RR_API_EINVAL, "request read error"); break; }
-        /* every RAW request already queued joins the batch (stop at a FLAT request) */
+        /* every RAW request already queued joins the batch (stop at a FLAT or SAVE request) */
         while (r.n < max_batch) {
             struct pollfd pf = {fd_req, POLLIN, 0};
             if (poll(&pf, 1, 0) <= 0 || !(pf.revents & POLLIN)) break;
             int d2;
             const int g = read_full(fd_req, &d2, sizeof d2);
             if (g != 1) break;   /* (a close is seen again at the top of the loop) */
-            if (d2 == RR_RDB_FLAT_TAG) { have_next = 1; next = d2; break; }
+            if (d2 == RR_RDB_FLAT_TAG || d2 == RR_RDB_SAVE_TAG) { have_next = 1; next = d2; break; }
             if (read_key(fd_req, d2, &r)) { rc = -1; break; }
         }
         if (rc || lookup(&r, get, user)) { drop_vals(&r, free_val); rc = fail(RR_API_EINVAL, "lookup failed (missing key)"); break; }
