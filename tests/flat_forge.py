@@ -1,6 +1,6 @@
 """Forged flat batches for the encoders: records, descriptors and an arena built from scratch, no
 decoder involved (include/rr_serdes.h: rr_encode_batch takes whatever flat batch its caller
-builds).  Three kinds of builders, all returning (values, elems, arena) as VALUE_DT / ELEM_DT /
+builds).  Four kinds of builders, all returning (values, elems, arena) as VALUE_DT / ELEM_DT /
 uint8 arrays:
 
   well_formed / decimal_lists   encodable values of every type, the empty ones included;
@@ -9,7 +9,10 @@ uint8 arrays:
   placement helpers             rejected values put where the kernels' walks change path: a run
                                 across a 256-value block edge, a run in front of a value at a
                                 16 KiB output-window edge, the first / last / every value, a
-                                block of more than 4,096 descriptors.
+                                block of more than 4,096 descriptors;
+  tiling helpers                a 61-value base batch whose value records are repeated over the
+                                same descriptors and arena, and the expected rdbsave output of
+                                the repeat from the reference's answer for the base alone.
 
 Nothing here decides what is encodable: tests/encode_expect.py states that rule.
 """
@@ -459,3 +462,91 @@ def cap_settings(offsets, accepted, total):
         end = int(offsets[acc[0] + 1])
         caps += [end, end - 1]
     return caps
+
+
+# ---- tiling: large batches from a small base, for the grid-stride tests -------------------------
+TILE_BASE = 61      # odd: a List at base index j sits at lane (j + 61 t) % 8 of its group in tile t
+TILE_FILL = 2       # list_fill of the tiled batches: a List of three entries is two nodes
+
+
+def _letters(rng, n):
+    return bytes(rng.integers(97, 123, n, dtype=np.uint8))    # never a decimal integer
+
+
+def tiling_base(seed=11):
+    """TILE_BASE values, short payloads: all eight types, a two-node List (under TILE_FILL), a List
+    of one 13-byte node, a rejected value (status != 0), a STRING in the integer form, a body
+    longer than a lane copies alone."""
+    f = Flat(seed)
+    rng = f.rng
+    L = rr.T_LIST_QUICKLIST
+    zl = pyoracle.build_ziplist([b"f", 3])
+    f.add(L, 0, [_letters(rng, 3), 7, _letters(rng, 5)])                # two nodes
+    f.add(rr.T_STRING, 0, [b"12345"])                                   # INT16
+    f.add(L, 0, [5])                                                    # one node of 13 bytes
+    f.add(rr.T_STRING, 0, [_letters(rng, 9)], status=3)                 # rejected
+    f.add(rr.T_SET_HT, 0, [_letters(rng, 4), b"77", _letters(rng, 2)])
+    f.add(rr.T_HASH_HT, 0, [_letters(rng, 3), _letters(rng, 6)])
+    f.add(rr.T_ZSET_SKIPLIST, 0, [_letters(rng, 3), ("score", _score_bits(1.5))])
+    f.add(rr.T_SET_INTSET, 2, [-3, 4, 500])
+    f.add(rr.T_HASH_ZIPLIST, 0, [("zl", zl)])
+    f.add(rr.T_ZSET_ZIPLIST, 0, [("zl", zl), 9])
+    f.add(rr.T_STRING, 1, [-(2**40)])
+    f.add(rr.T_STRING, 8, [_letters(rng, 70)])                          # copied by the whole wave
+    f.add(L, 0, [])
+    while len(f.values) < TILE_BASE:
+        k = len(f.values) % 6
+        if k == 0:
+            f.add(L, 0, [(_letters(rng, int(rng.integers(0, 9))) if q % 2 else int(rng.integers(-900, 900)))
+                         for q in range(int(rng.integers(1, 6)))])
+        elif k == 1:
+            f.add(rr.T_STRING, 0, [_letters(rng, int(rng.integers(0, 60)))])
+        elif k == 2:
+            f.add(rr.T_SET_HT, 0, [_letters(rng, int(rng.integers(1, 12))) for _ in range(int(rng.integers(0, 4)))])
+        elif k == 3:
+            f.add(rr.T_STRING, 1, [int(rng.integers(-2**33, 2**33))])
+        elif k == 4:
+            f.add(L, 0, [_letters(rng, 40), _letters(rng, 2)])
+        else:
+            f.add(rr.T_SET_INTSET, 4, [int(x) for x in rng.integers(-10**6, 10**6, int(rng.integers(0, 4)))])
+    return f.done()
+
+
+def tile_records(values, n):
+    """n value records: the base's repeated over the same descriptors and arena, the last tile cut."""
+    return np.tile(values, (n + len(values) - 1) // len(values))[:n].copy()
+
+
+def tiling_reference(values, elems, arena, fill=TILE_FILL):
+    """(base_ref, base_pays) for tile_expect: the reference on the base batch, and on each of its
+    values alone for that value's share of totals.payload."""
+    import rdb_reference as ref
+    base_ref = ref.save_batch(values, elems, arena, fill)
+    pays = [ref.save_batch(values[i:i + 1], elems, arena, fill)[4]["payload"] for i in range(len(values))]
+    return base_ref, pays
+
+
+def tile_expect(base_values,base_ref, base_pays, n, data_cap=None):
+    """What rr_rdbsave_batch gives for tile_records(base_values, n), from the reference's answer
+    for the base alone (base_ref: rdb_reference.save_batch without a data_cap) and base_pays, each
+    base value's totals.payload when saved alone: (types, data, offsets, status, totals).  data
+    holds offsets[n] bytes whatever data_cap is: offsets never decrease, so the values written are
+    those before the first saveable one that ends past data_cap, and a test compares
+    data[:offsets[j]] for that j.  tests/test_rdbsave.py holds this shortcut to save_batch on the
+    tiled records themselves."""
+    types, bdata, boffs, bstatus, _, _ = base_ref
+    m = len(types)
+    reps = (n + m - 1) // m
+    sizes = np.tile(np.diff(boffs.astype(np.int64)), reps)[:n]
+    offsets = np.zeros(n + 1, np.uint64)
+    offsets[1:] = np.cumsum(sizes)
+    total = int(offsets[n])
+    status = np.tile(bstatus, reps)[:n].copy()
+    pays = np.tile(np.asarray(base_pays, np.int64), reps)[:n]
+    if data_cap is not None:
+        status[(status == 0) & (offsets[1:] > np.uint64(data_cap))] = rr.E_CAPACITY
+    data = np.tile(bdata, reps)[:total].copy()
+    n_elems = int(np.tile(base_values["n_elems"].astype(np.int64), reps)[:n].sum())
+    totals = {"n_elems": n_elems, "bytes": total,
+              "n_bad": int((status != 0).sum()), "payload": int(pays[status == 0].sum())}
+    return np.tile(types, reps)[:n].copy(), data, offsets, status, totals

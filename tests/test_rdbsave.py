@@ -143,6 +143,42 @@ def test_bound_holds_for_reference_output():
         assert total <= rr.rdbsave_bound(values, elems)
 
 
+def test_tiled_expectation_equals_reference_on_tiled_records():
+    """The shortcut of tests/test_gpu_rdbsave_scale.py (flat_forge.tile_expect: the reference once on
+    a 61-value base, its payloads repeated) against save_batch on the repeated records themselves:
+    three whole tiles, a cut last tile, and a data_cap in the middle of a value of the third tile."""
+    import flat_forge as ff
+    values, elems, arena = ff.tiling_base()
+    base_ref, pays = ff.tiling_reference(values, elems, arena)
+    assert len(values) == ff.TILE_BASE and len(set(values["type"].tolist())) == 8
+    assert int(base_ref[2][-1]) <= 40 * ff.TILE_BASE          # short payloads: the big batches stay cheap
+    st = base_ref[3]
+    assert values["status"][3] != 0 and st[3] == rr.E_ENCODE and (np.delete(st, 3) == 0).all()
+    nodes = lambda i: base_ref[5][i][0]                       # rdbSaveLen(node count), one byte here
+    assert nodes(0) == 2 and base_ref[5][2] == b"\x01\x0d" + ref.list_nodes([b"5"], ff.TILE_FILL)[0]
+    assert len(ref.list_nodes([b"5"], ff.TILE_FILL)[0]) == 13 and base_ref[5][1] == b"\xC1\x39\x30"
+    sizes = np.diff(base_ref[2].astype(np.int64))
+    for n, cut_at in ((3 * ff.TILE_BASE, None), (2 * ff.TILE_BASE + 22, None), (3 * ff.TILE_BASE, 2 * ff.TILE_BASE + 5)):
+        tv = ff.tile_records(values, n)
+        cap = None
+        if cut_at is not None:
+            assert sizes[cut_at % ff.TILE_BASE] > 1
+            full = ff.tile_expect(values, base_ref, pays, n)[2]
+            cap = (int(full[cut_at]) + int(full[cut_at + 1])) // 2
+        want = ref.save_batch(tv, elems, arena, ff.TILE_FILL, cap)
+        types, data, offsets, status, totals = ff.tile_expect(values, base_ref, pays, n, cap)
+        assert np.array_equal(types, want[0]) and np.array_equal(offsets, want[2])
+        assert np.array_equal(status, want[3]) and totals == want[4]
+        if cap is None:
+            assert np.array_equal(data, want[1])
+        else:
+            j = int(np.nonzero(status == rr.E_CAPACITY)[0][0])
+            assert j == cut_at and (status[j:] != 0).all() and (status[:j] == np.tile(st, 3)[:j]).all()
+            # save_batch leaves unwritten bytes zero; nothing is written from offsets[j] on
+            assert np.array_equal(data[:int(offsets[j])], want[1][:int(offsets[j])])
+            assert not want[1][int(offsets[j]):].any()
+
+
 def test_library_exports_every_rdbsave_symbol():
     """include/rr_rdbsave.h: every declared function is named rr_rdbsave_*, exported and listed."""
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rr_rdbsave.h")).read(), flags=re.S)
