@@ -17,11 +17,14 @@
 //                     instantiation: input and output in global memory, the same chain, the same
 //                     verdicts.
 //   lz4_bound_kernel  thread per block: the output slot sizes
-//   lz4_comp_kernel   wave per block.  A hash table of 16-bit positions in LDS (RR_LZ4_HASH_LOG),
-//                     64 consecutive positions hashed and probed a round, the first lane whose
-//                     candidate matches wins, the match extended 64 bytes a step.  Nothing
-//                     depends on timing: the table's update is a max (see insert()), so the same
-//                     input gives the same bytes on every run.
+//   lz4_comp_kernel   wave per block.  Two hash tables in LDS (RR_LZ4_HASH_LOG): the latest
+//                     position of each hash (16 bits), and a quarter as many entries with the
+//                     chunk's first position of each hash beside 16 more hash bits.  64 consecutive
+//                     positions hashed and probed a round, the first lane whose candidate (the
+//                     latest, else the first) matches wins, the match extended 64 bytes a step.
+//                     Nothing depends on timing: the tables' updates are a max and a min (see
+//                     insert(), insert_first()), so the same input gives the same bytes on
+//                     every run.
 //   (rr_snappy.hip)   slots -> packed output
 //
 // Every loop advances its input position or exits; no wave waits on another.
@@ -42,12 +45,14 @@ constexpr uint32_t WAVE = 64;
 #endif
 constexpr uint32_t LZ4_DEC_WIN = RR_LZ4_DEC_WIN;
 static_assert(LZ4_DEC_WIN % 16 == 0 && LZ4_DEC_WIN >= 1024 && LZ4_DEC_WIN <= 65536 - 64, "window bytes");
-// log2 of the compressor's hash table entries (u16 positions: 8 KiB of LDS per wave at 12)
+// log2 of the entries of the compressor's hash table of latest positions (u16: 8 KiB of LDS per
+// wave at 12); the table of first positions has a quarter as many, 32 bits each (4 KiB)
 #ifndef RR_LZ4_HASH_LOG
 #define RR_LZ4_HASH_LOG 12
 #endif
 constexpr uint32_t HLOG = RR_LZ4_HASH_LOG, HSIZE = 1u << HLOG;
-static_assert(HLOG >= 8 && HLOG <= 15, "hash table size");
+static_assert(HLOG >= 8 && HLOG <= 14, "hash table size");
+constexpr uint32_t FLOG = HLOG - 2, FSIZE = 1u << FLOG;
 constexpr uint32_t CHUNK = 1u << 16;   // positions a table entry can hold
 constexpr uint32_t MINMATCH = 4, LASTLITERALS = 5, MFLIMIT = 12, FASTLOOP = 64;   // lz4.c:189-195
 constexpr uint32_t BAIL = 0xFF;        // (internal) leave the LDS window for the global path
@@ -429,13 +434,30 @@ __device__ __forceinline__ void insert(lds_u16 *tab, bool ins, uint32_t h, uint3
     }
 }
 
+// first[h] = the smallest of the words (position << 16 | 16 hash bits) the lanes with `ins` hold
+// for h, where the entry is still empty (0: the caller keeps the chunk's first position and every
+// other one with its hash out of `ins`, so that entry stays 0 and stands for it).  Positions
+// grow from round to round, so an entry is written in one round only; inside it the lanes that
+// hold a smaller position than the one that landed store again: the result is the minimum
+// whichever store the hardware lets win.  At most 64 passes.
+__device__ __forceinline__ void insert_first(lds_u32 *first, bool ins, uint32_t h, uint32_t word, uint32_t round0) {
+    for (;;) {
+        const uint32_t cur = ins ? first[h] : 0u;
+        ins = ins && (cur == 0 || ((cur >> 16) >= round0 && cur > word));   // (round0: this round's first position)
+        if (!__ballot(ins)) return;
+        if (ins) first[h] = word;
+    }
+}
+
 __global__ __launch_bounds__(WAVE) void lz4_comp_kernel(const uint8_t *__restrict__ in, uint64_t in_cap,
                                                         const uint64_t *__restrict__ in_offs, uint64_t n,
                                                         uint8_t *__restrict__ slots,
                                                         const uint64_t *__restrict__ slot_offs,
                                                         uint64_t *__restrict__ sizes) {
     __shared__ uint16_t tab_mem[HSIZE];
+    __shared__ uint32_t first_mem[FSIZE];
     lds_u16 *tab = (lds_u16 *)tab_mem;
+    lds_u32 *first = (lds_u32 *)first_mem;
     const uint32_t lane = lane_id();
     for (uint64_t b = blockIdx.x; b < n; b += gridDim.x) {
         const uint64_t c0 = in_offs[b];
@@ -464,21 +486,34 @@ __global__ __launch_bounds__(WAVE) void lz4_comp_kernel(const uint8_t *__restric
             // mlim (the last 5 bytes are literals): lz4_Block_format.md, end of block restrictions
             const uint32_t mfl = len - MFLIMIT, mlim = len - LASTLITERALS;
             uint32_t ip = 0, cb = 0;   // cb: the chunk's first position (table entries are relative to it)
+            uint32_t h0 = 0;           // first's hash at cb: first[h0] stays 0, which stands for cb
             bool fresh = true;
             while (ip <= mfl) {
                 if (fresh || ip - cb >= CHUNK) {   // a new 64 KiB chunk: its own table; pending literals carry over
                     cb = ip;
                     for (uint32_t k = lane; k < HSIZE / 2; k += WAVE) ((lds_u32 *)tab)[k] = 0;
+                    for (uint32_t k = lane; k < FSIZE; k += WAVE) first[k] = 0;
                     fresh = false;
                 }
                 const uint32_t P = ip + lane;
                 const bool valid = P <= mfl && P - cb < CHUNK;
                 const uint32_t x = F.ld32(valid ? P : 0u), h = hash4(x);
-                const uint32_t c = cb + (valid ? (uint32_t)tab[h] : 0u);   // (an empty entry reads as the chunk's first position)
-                const bool hit = valid && c < P && F.ld32(c) == x;
+                // the latest position with this hash; where that is no match, the chunk's first one
+                // (a repeat from far back, which later positions have pushed out of tab), read
+                // only where the entry's 16 hash bits agree
+                const uint32_t hv = x * 2654435761u, hf = hv >> (32 - FLOG), tag = (hv >> (16 - FLOG)) & 0xFFFFu;
+                if (ip == cb) h0 = rdl(hf, 0);
+                const uint32_t c1 = cb + (valid ? (uint32_t)tab[h] : 0u);   // (an empty entry reads as the chunk's first position)
+                const uint32_t e = valid ? first[hf] : 0u, c2 = cb + (e >> 16);
+                const bool hit1 = valid && c1 < P && F.ld32(c1) == x;
+                const bool may2 = valid && !hit1 && c2 != c1 && c2 < P && (e ? (e & 0xFFFFu) == tag : hf == h0);
+                const bool hit = hit1 || (may2 && F.ld32(c2) == x);
+                const uint32_t c = hit1 ? c1 : c2;
                 const uint64_t bal = __ballot(hit);
                 const uint32_t sl = bal ? (uint32_t)__builtin_ctzll(bal) : WAVE;
                 insert(tab, valid && lane <= sl, h, P - cb);
+                if (ip - cb < 4 * FSIZE)   // (after four positions an entry the table is full but for 2 %)
+                    insert_first(first, valid && lane <= sl && hf != h0, hf, ((P - cb) << 16) | tag, ip - cb);
                 if (!bal) {
                     ip += WAVE;
                     continue;

@@ -125,19 +125,15 @@ def decode(stream: bytes):
     return decode_block(stream[h[1]:], h[0])
 
 
-def check_encoder_rules(stream: bytes):
-    """The encoder-side end rules (lz4_Block_format.md, "End of block restrictions") on a framed
-    stream decode() accepts: the last 5 bytes are literals and the last match starts at least 12
-    bytes before the end; a block below 13 bytes is one literal run.  Returns None or a message."""
-    h = read_varint32(stream)
-    if h is None:
-        return "bad preamble"
-    N, src = h[0], stream[h[1]:]
-    ip = op = 0
-    nseq = 0
+def sequences(src: bytes):
+    """The token walk of a raw block decode_block() accepts: (L, None, None) for the last literal
+    run, (L, offset, M) with M the whole match length for every sequence before it; None as the
+    last item when the block ends before its last literal run."""
+    ip = 0
     while True:
         if ip >= len(src):
-            return "block ends before its last literal run"
+            yield None
+            return
         token = src[ip]
         ip += 1
         L, M = token >> 4, token & 15
@@ -149,16 +145,9 @@ def check_encoder_rules(stream: bytes):
                 if s != 255:
                     break
         ip += L
-        op += L
-        nseq += 1
         if ip == len(src):
-            if op != N:
-                return f"{op} bytes, {N} announced"
-            if N >= 1 and nseq > 1 and L < LASTLITERALS:
-                return f"last literal run of {L} bytes"
-            return None
-        if N < MFLIMIT + 1:
-            return "a match in a block below 13 bytes"
+            yield L, None, None
+            return
         offset = src[ip] | (src[ip + 1] << 8)
         ip += 2
         if M == 15:
@@ -168,7 +157,32 @@ def check_encoder_rules(stream: bytes):
                 M += s
                 if s != 255:
                     break
-        M += MINMATCH
+        yield L, offset, M + MINMATCH
+
+
+def check_encoder_rules(stream: bytes):
+    """The encoder-side end rules (lz4_Block_format.md, "End of block restrictions") on a framed
+    stream decode() accepts: the last 5 bytes are literals and the last match starts at least 12
+    bytes before the end; a block below 13 bytes is one literal run.  Returns None or a message."""
+    h = read_varint32(stream)
+    if h is None:
+        return "bad preamble"
+    N, src = h[0], stream[h[1]:]
+    op = nseq = 0
+    for q in sequences(src):
+        if q is None:
+            return "block ends before its last literal run"
+        L, offset, M = q
+        op += L
+        nseq += 1
+        if offset is None:
+            if op != N:
+                return f"{op} bytes, {N} announced"
+            if N >= 1 and nseq > 1 and L < LASTLITERALS:
+                return f"last literal run of {L} bytes"
+            return None
+        if N < MFLIMIT + 1:
+            return "a match in a block below 13 bytes"
         if offset == 0 or offset > op:
             return f"offset {offset} at output {op}"
         if op > N - MFLIMIT:

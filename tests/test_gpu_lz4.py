@@ -3,7 +3,9 @@ decompression against the Python statement of the acceptance rule (tests/lz4_ref
 hand-built and the mutated streams, the LDS window against the global path, the window's edges,
 batch sizes and the grid-stride loop; compression by round trip under the reference decoder and
 pyarrow's lz4_raw, the encoder-side end rules, the bound, determinism, and the size against
-pyarrow's on the same blocks."""
+pyarrow's on the same blocks.  tests/test_gpu_lz4_window.py pins what this module meets only by
+chance: the window's bail-out on its boundary, the copies over length x offset x alignment, input
+and output alignment, the length extensions' second round, a caller's stream and graph replay."""
 import functools
 import os
 import sys
