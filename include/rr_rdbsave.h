@@ -7,7 +7,8 @@
  * the flat form of rr_format.h, so the child needs no object: it copies type | key | payload.
  *
  * For value i the call gives a type byte types[i] and a payload data[offsets[i] .. offsets[i+1]).
- * The payload is what rdbSaveObject (rdb.c:761-900) writes, with `rdbcompression no`, for the object
+ * The payload is what rdbSaveObject (rdb.c:761-900) writes, with `rdbcompression no` (with
+ * RR_RDBSAVE_LZF: with the LZF string form of `rdbcompression yes`, see "LZF" below), for the object
  * desObject builds from the blob rr_encode_batch writes for that value.  types[i] is
  * rdbSaveObjectType's byte (rdb.c:632-670); the RDB numbers (rdb.h:75-92) equal the rock tags the
  * flat form carries — STRING 0, SET 2, HASH 4, ZSET_2 5, SET_INTSET 11, ZSET_ZIPLIST 12,
@@ -59,8 +60,37 @@
  *                   0xF0; int32 0xD0; else 0xE0, little-endian (:507-534).  A STR descriptor whose
  *                   bytes pass zipTryEncoding is such an entry too, as it is after desList.
  *
- * Two deviations, both loadable by every RDB loader:
- *   - no LZF: the output is the reference's under `rdbcompression no`;
+ * LZF (rr_rdbsave_opts.flags & RR_RDBSAVE_LZF; the reference's default, config.c:2153
+ * server.rdb_compression = 1).  Under `rdbcompression yes` rdbSaveRawString sends every string of
+ * more than 20 bytes through rdbSaveLzfStringObject first (rdb.c:426-431, :348-364).  With the flag
+ * the same happens at every rdbSaveRawString site whose bytes lie in the arena: the STR descriptor of
+ * a RAW or EMBSTR String, SET_HT members, HASH_HT fields and values, ZSET_SKIPLIST members (not the
+ * scores), the ZLRAW bytes of a HASH_ZIPLIST or ZSET_ZIPLIST.  The integer attempt comes first, as
+ * without the flag; it applies to len <= 11 only, so the two never meet.  If len > 20 the string is
+ * compressed, and if the stream has clen != 0 && clen <= len - 4 the string is written as
+ *     0xC3 | rdbSaveLen(clen) | rdbSaveLen(len) | stream
+ * (rdbSaveLzfBlob, rdb.c:323-346; 0xC3 = (RDB_ENCVAL << 6) | RDB_ENC_LZF), otherwise raw as above.
+ *   The stream is what lzf_decompress (lzf_d.c:68-184) reads: a control byte c < 32 is followed by
+ * c + 1 literal bytes; otherwise l = c >> 5, plus the next byte when l == 7, the offset is
+ * ((c & 0x1f) << 8 | next byte) + 1, and l + 2 bytes are copied from op - offset one at a time
+ * (overlap allowed).  So a match is 3..264 bytes at distance 1..8192 and a literal run 1..32 bytes.
+ *   The contract is that of rr_lz4.h: a valid stream, deterministic, not the CPU compressor's bytes.
+ * lzf_decompress(stream, clen, buf, len) returns len and gives the string back.  A string's stream
+ * depends on its bytes and length only: not on its arena address or alignment, its output address,
+ * its neighbours in the batch, the grid, or the run.  lzf_c.c's own bytes cannot be the goal: it
+ * compresses over an uninitialised table (lzfP.h:95, INIT_HTAB 0), so they are not reproducible, and
+ * its out-of-space tests (lzf_c.c:167-168, :259, :272) are conservative by a few bytes.  Which
+ * strings take the LZF form may so differ from a given reference run; every loader takes either.
+ * A string of 0x7FFFFFF0 bytes or more is written raw.
+ *   These stay raw with the flag set: INT Strings (rdbSaveLongLongAsStringObject), the intset blob
+ * and the quicklist nodes (both assembled by the kernels, not in the arena).
+ *   The SAVE request of the pipe mode below keeps the default options, without LZF: carrying options
+ * over the pipe needs a new entry point on the child's side, which is a change of its own.
+ *
+ * Deviations, all loadable by every RDB loader:
+ *   - LZF: none without RR_RDBSAVE_LZF (the output is the reference's under `rdbcompression no`);
+ *     with it, intset blobs and List nodes of more than 20 bytes stay raw where the reference
+ *     would try LZF, and the streams are this library's, not lzf_c.c's;
  *   - SET_HT and HASH_HT are written in the flat form's order.  The reference writes dictNext order
  *     under a per-process random hash seed, so its order is not reproducible; any order loads to
  *     the same object.
@@ -83,11 +113,13 @@ extern "C" {
 #endif
 
 #define RR_RDBSAVE_DEFAULT_FILL (-2)   /* OBJ_LIST_MAX_ZIPLIST_SIZE, server.h */
+#define RR_RDBSAVE_LZF 1u              /* rr_rdbsave_opts.flags: the LZF string form ("LZF" above) */
 
 typedef struct rr_rdbsave_opts {
     int32_t list_fill;      /* list-max-ziplist-size; clamped to [-5, 32767] as quicklistSetFill
                                does for its 16-bit field (quicklist.c:117-124, quicklist.h:78) */
-    uint32_t rsv;           /* 0 */
+    uint32_t flags;         /* 0 or RR_RDBSAVE_LZF; any other bit: RR_API_EINVAL from both calls.
+                               0 gives the bytes of opts == NULL but for list_fill */
 } rr_rdbsave_opts;
 
 /* Upper bound on the bytes of a batch of n values with n_elems descriptors whose STR / ZLRAW
@@ -100,12 +132,16 @@ typedef struct rr_rdbsave_opts {
  *                  ziplist header and end byte (11) are charged to its first entry, whose prevlen
  *                  is always 1 byte: 16 + 1 + 5 + len = 22 + len as a string, 16 + 1 + 9 = 26 as
  *                  an integer; every later entry costs at most 10 + len or 14.  So 26 + len holds
- *                  for every entry */
+ *                  for every entry
+ * The bound holds with RR_RDBSAVE_LZF too: an LZF string costs 1 + rdbSaveLen(clen) +
+ * rdbSaveLen(len) + clen <= 1 + 5 + 5 + (len - 4) = len + 7, within the 26 + len of its descriptor. */
 uint64_t rr_rdbsave_bound(uint64_t n, uint64_t n_elems, uint64_t payload_bytes);
 
 /* Device-resident: every pointer on ctx's device.  out->n == in->n; out->data 16-byte aligned;
  * writes out->offsets[0..n], out->data, types[0..n), status[0..n) and *d_totals.  opts may be NULL
- * (list_fill -2).  Five launches on `stream` (sizes, scan, emit, two for the Lists), no host synchronisation. */
+ * (list_fill -2, flags 0).  Five launches on `stream` (sizes, scan, emit, two for the Lists), no host
+ * synchronisation.  With RR_RDBSAVE_LZF the context's scratch also holds 4 bytes per descriptor
+ * (in->elem_cap), so rr_ctx_reserve or a warm call comes before a graph capture, as for every call. */
 int rr_rdbsave_batch(rr_ctx *ctx, const rr_flat_batch *in, rr_blob_batch *out, uint8_t *types,
                      uint8_t *status, rr_totals *d_totals, const rr_rdbsave_opts *opts, void *stream);
 

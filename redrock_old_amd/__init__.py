@@ -62,7 +62,7 @@ class FlatBatch(C.Structure):
 
 
 class RdbSaveOpts(C.Structure):
-    _fields_ = [("list_fill", C.c_int32), ("rsv", C.c_uint32)]
+    _fields_ = [("list_fill", C.c_int32), ("flags", C.c_uint32)]   # flags: 0 or RDBSAVE_LZF
 
 
 class Shard(C.Structure):
@@ -110,6 +110,7 @@ HOST_EXPORTS = ["rr_host_reserve", "rr_host_decode_value", "rr_host_check_value"
 # include/rr_rdbsave.h (flat batch -> RDB value payloads for the snapshot child, row f4)
 RDBSAVE_EXPORTS = ["rr_rdbsave_bound", "rr_rdbsave_batch", "rr_rdbsave_batch_host", "rr_rdbsave_request",
                    "rr_rdbsave_result_free"]
+RDBSAVE_LZF = 1                 # rr_rdbsave_opts.flags: strings of more than 20 bytes try the LZF form
 E_CAPACITY, E_ENCODE = 11, 12   # the per-value statuses of rdbsave (RR_E_*, rr_format.h)
 SNAPPY_STATUS = {0: "OK", 1: "HEADER", 2: "TRUNC", 3: "OFFSET", 4: "OVERFLOW", 5: "LENGTH", 6: "CAPACITY"}
 LZ4_STATUS = dict(SNAPPY_STATUS)   # RR_LZ4_* parallel RR_SNAPPY_*
@@ -581,8 +582,9 @@ class Engine:
 
     # ---- RDB value payloads (include/rr_rdbsave.h) -----------------------------------------
     def rdbsave_host(self, values: np.ndarray, elems: np.ndarray, arena: np.ndarray, list_fill: int = -2,
-                     data_cap: int | None = None):
-        """Flat batch -> (types, data, offsets, status, totals): the bytes rdbSaveObject writes per value."""
+                     data_cap: int | None = None, lzf: bool = False, flags: int | None = None):
+        """Flat batch -> (types, data, offsets, status, totals): the bytes rdbSaveObject writes per value.
+        lzf: RR_RDBSAVE_LZF (`rdbcompression yes`); flags, when given, is the options' word as it is."""
         n = len(values)
         values = np.ascontiguousarray(values, VALUE_DT)
         elems = np.ascontiguousarray(elems, ELEM_DT)
@@ -594,19 +596,20 @@ class Engine:
         types = np.zeros(max(n, 1), np.uint8)
         status = np.zeros(max(n, 1), np.uint8)
         t = Totals()
-        opts = RdbSaveOpts(list_fill, 0)
+        opts = RdbSaveOpts(list_fill, (RDBSAVE_LZF if lzf else 0) if flags is None else flags)
         _check(self._L.rr_rdbsave_batch_host(self._ctx, _ptr(values), _ptr(elems), len(elems), _ptr(arena), arena.size,
                                              n, C.byref(opts), _ptr(data), data_cap, _ptr(offsets), _ptr(types),
                                              _ptr(status), C.byref(t)))
         return types[:n], data[:min(int(offsets[-1]), data_cap)], offsets, status[:n], t.as_dict()
 
     def rdbsave_device(self, values, elems, arena, out_data, out_offsets, types, status, totals, list_fill: int = -2,
-                       stream=None):
-        """rr_rdbsave_batch on torch CUDA tensors (uint8 views of the flat records); no host sync."""
+                       stream=None, lzf: bool = False, flags: int | None = None):
+        """rr_rdbsave_batch on torch CUDA tensors (uint8 views of the flat records); no host sync.
+        lzf: RR_RDBSAVE_LZF (`rdbcompression yes`); flags, when given, is the options' word as it is."""
         n = out_offsets.numel() - 1
         inb = FlatBatch(values.data_ptr(), elems.data_ptr(), arena.data_ptr(), n, elems.numel() // 16, arena.numel())
         outb = BlobBatch(out_data.data_ptr(), out_offsets.data_ptr(), n, out_data.numel())
-        opts = RdbSaveOpts(list_fill, 0)
+        opts = RdbSaveOpts(list_fill, (RDBSAVE_LZF if lzf else 0) if flags is None else flags)
         _check(self._L.rr_rdbsave_batch(self._ctx, C.byref(inb), C.byref(outb), C.c_void_p(types.data_ptr()),
                                         C.c_void_p(status.data_ptr()), C.c_void_p(totals.data_ptr()), C.byref(opts),
                                         _sp(stream)))

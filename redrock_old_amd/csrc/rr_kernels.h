@@ -57,10 +57,11 @@ hipError_t rr_launch_lz4_decompress(const uint8_t *in, uint64_t in_cap, const ui
                                     hipStream_t stream);
 hipError_t rr_launch_lz4_compress(const uint8_t *in, uint64_t in_cap, const uint64_t *in_offs, uint64_t n, uint8_t *out,
                                   uint64_t *out_offs, uint64_t *scratch, uint64_t slot_bytes, hipStream_t stream);
-/* rr_rdbsave.hip (include/rr_rdbsave.h): sizes, scan, emit; scratch of rr_rdbsave_scratch_words(n) */
-uint64_t rr_rdbsave_scratch_words(uint64_t n);
+/* rr_rdbsave.hip (include/rr_rdbsave.h): sizes, scan, emit; scratch of rr_rdbsave_scratch_words(n,
+ * lzf ? elem_cap : 0).  lzf: RR_RDBSAVE_LZF, the LZF instantiations of the size and emit kernels */
+uint64_t rr_rdbsave_scratch_words(uint64_t n, uint64_t lzf_elems);
 hipError_t rr_launch_rdbsave(const rr_value *values, const rr_elem *elems, uint64_t elem_cap, const uint8_t *arena,
-                             uint64_t arena_cap, uint64_t n, int list_fill, uint8_t *out, uint64_t cap, uint64_t *offsets,
+                             uint64_t arena_cap, uint64_t n, int list_fill, int lzf, uint8_t *out, uint64_t cap, uint64_t *offsets,
                              uint8_t *types, uint8_t *status, uint64_t *scratch, rr_totals *totals, hipStream_t stream);
 hipError_t rr_launch_shard_plan(const uint64_t *offsets, uint64_t n, uint32_t g, uint64_t *plan, hipStream_t stream);
 hipError_t rr_launch_offsets_rebase(uint64_t *offs, uint64_t count, uint64_t sub, hipStream_t stream);

@@ -32,10 +32,13 @@ int rr_rdbsave_batch(rr_ctx *c, const rr_flat_batch *in, rr_blob_batch *out, uin
     if (!out->offsets) return fail(RR_API_EINVAL, "NULL offsets");
     if (in->n && (!in->values || !out->data || !types || !status)) return fail(RR_API_EINVAL, "NULL buffer");
     if ((uintptr_t)out->data & 15) return fail(RR_API_EINVAL, "out->data must be 16-byte aligned");
+    if (opts && (opts->flags & ~RR_RDBSAVE_LZF)) return fail(RR_API_EINVAL, "rr_rdbsave_opts.flags: unknown bit");
+    const int lzf = opts && (opts->flags & RR_RDBSAVE_LZF);
     HIPCHK(hipSetDevice(c->device));
-    int rc = rr_ensure_scratch(c, rr_rdbsave_scratch_words(in->n), (hipStream_t)stream);
+    /* the LZF form keeps a u32 per descriptor between the size and the emit pass */
+    int rc = rr_ensure_scratch(c, rr_rdbsave_scratch_words(in->n, lzf ? in->elem_cap : 0), (hipStream_t)stream);
     if (rc) return rc;
-    HIPCHK(rr_launch_rdbsave(in->values, in->elems, in->elem_cap, in->arena, in->arena_cap, in->n, clamp_fill(opts),
+    HIPCHK(rr_launch_rdbsave(in->values, in->elems, in->elem_cap, in->arena, in->arena_cap, in->n, clamp_fill(opts), lzf,
                              out->data, out->data_cap, out->offsets, types, status, c->scratch, d_totals,
                              (hipStream_t)stream));
     return rr_mark_scratch(c, (hipStream_t)stream);
@@ -49,6 +52,7 @@ int rr_rdbsave_batch_host(rr_ctx *c, const rr_value *values, const rr_elem *elem
                           rr_totals *totals) {
     if (!c || !offsets || (n && (!values || !data || !types || !status))) return fail(RR_API_EINVAL, "NULL argument");
     if ((n_elems && !elems) || (arena_bytes && !arena)) return fail(RR_API_EINVAL, "NULL argument");
+    if (opts && (opts->flags & ~RR_RDBSAVE_LZF)) return fail(RR_API_EINVAL, "rr_rdbsave_opts.flags: unknown bit");
     HIPCHK(hipSetDevice(c->device));
     GROW(c->d_vals, c->c_vals, (n ? n : 1) * sizeof(rr_value));
     GROW(c->d_elems, c->c_elems, (n_elems ? n_elems : 1) * sizeof(rr_elem));

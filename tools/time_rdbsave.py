@@ -1,8 +1,9 @@
 """Diagnostics: time rr_rdbsave_batch (include/rr_rdbsave.h) beside rr_encode_batch on the same flat
 batch, device-resident, HIP events: config batches decoded on the device, and a List-only batch.
 Each figure is the call time (every launch of the call) over `steps` calls after a warm-up call,
-three trials, fastest and slowest shown.
-Usage: python tools/time_rdbsave.py [configs, e.g. 2,3,4] [n] [steps] [n_lists] [entries per list]"""
+three trials, fastest and slowest shown.  --lzf: the call again with RR_RDBSAVE_LZF, and its output
+bytes as a fraction of the output without it.
+Usage: python tools/time_rdbsave.py [--lzf] [configs, e.g. 2,3,4] [n] [steps] [n_lists] [entries per list]"""
 import os
 import struct
 import sys
@@ -14,6 +15,8 @@ import torch  # noqa: E402
 
 import redrock_old_amd as rr  # noqa: E402
 
+LZF = "--lzf" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--lzf"]
 cfgs = [int(c) for c in (sys.argv[1] if len(sys.argv) > 1 else "2,3,4").split(",")]
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 1_000_000
 steps = int(sys.argv[3]) if len(sys.argv) > 3 else 10
@@ -84,6 +87,11 @@ def run(name, data, offs):
     print(f"  rr_encode_batch   {te[0]:.3f}-{te[1]:.3f} ms  {nv / te[0] / 1e3:.2f} M values/s  {eb / te[0] / 1e6:.1f} GB/s out")
     print(f"  rr_rdbsave_batch  {tr[0]:.3f}-{tr[1]:.3f} ms  {nv / tr[0] / 1e3:.2f} M values/s  {rb / tr[0] / 1e6:.1f} GB/s out"
           f"  payload bytes={rb} bad={bad}  time vs encode x{tr[0] / te[0]:.2f}")
+    if LZF:
+        tz = timed(lambda: eng.rdbsave_device(d_vals, els, d_arena, out, o_off, o_ty, o_st, d_tot, stream=s, lzf=True))
+        zb, zbad = int(o_off[-1].item()), int(d_tot[2].item())
+        print(f"  ... with LZF      {tz[0]:.3f}-{tz[1]:.3f} ms  {nv / tz[0] / 1e3:.2f} M values/s  {zb / tz[0] / 1e6:.1f} GB/s out"
+              f"  payload bytes={zb} bad={zbad}  output x{zb / rb:.3f} of flag off  time x{tz[0] / tr[0]:.2f} of flag off")
 
 
 for cfg in cfgs:
