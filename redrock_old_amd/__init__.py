@@ -65,6 +65,18 @@ class RdbSaveOpts(C.Structure):
     _fields_ = [("list_fill", C.c_int32), ("flags", C.c_uint32)]   # flags: 0 or RDBSAVE_LZF
 
 
+class RdbLoadOpts(C.Structure):
+    """rr_rdbload_opts (include/rr_rdbload.h); the defaults are the reference's (config.c:2261-2267)."""
+    _fields_ = [("lru", C.c_uint32), ("set_max_intset_entries", C.c_uint32), ("hash_max_ziplist_entries", C.c_uint32),
+                ("hash_max_ziplist_value", C.c_uint32), ("zset_max_ziplist_entries", C.c_uint32),
+                ("zset_max_ziplist_value", C.c_uint32), ("flags", C.c_uint32)]
+
+    def __init__(self, lru=0, set_max_intset_entries=512, hash_max_ziplist_entries=512, hash_max_ziplist_value=64,
+                 zset_max_ziplist_entries=128, zset_max_ziplist_value=64, flags=0):
+        super().__init__(lru, set_max_intset_entries, hash_max_ziplist_entries, hash_max_ziplist_value,
+                         zset_max_ziplist_entries, zset_max_ziplist_value, flags)
+
+
 class Shard(C.Structure):
     _fields_ = [("v0", C.c_uint64), ("v1", C.c_uint64), ("b0", C.c_uint64), ("b1", C.c_uint64)]
 
@@ -112,6 +124,12 @@ RDBSAVE_EXPORTS = ["rr_rdbsave_bound", "rr_rdbsave_batch", "rr_rdbsave_batch_hos
                    "rr_rdbsave_result_free"]
 RDBSAVE_LZF = 1                 # rr_rdbsave_opts.flags: strings of more than 20 bytes try the LZF form
 E_CAPACITY, E_ENCODE = 11, 12   # the per-value statuses of rdbsave (RR_E_*, rr_format.h)
+# include/rr_rdbload.h (RDB value payloads -> rock blobs, the load direction of rr_rdbsave.h)
+RDBLOAD_EXPORTS = ["rr_rdbload_bound", "rr_rdbload_batch", "rr_rdbload_batch_host"]
+RDBLOAD_E_TYPE, RDBLOAD_E_LEN, RDBLOAD_E_TRUNC, RDBLOAD_E_LZF = 32, 33, 34, 35
+RDBLOAD_E_EXTRA, RDBLOAD_E_ZIPLIST, RDBLOAD_E_CONVERT = 36, 37, 38
+RDBLOAD_LZF_NODE_MAX = 10240    # the longest List node taken in the LZF form
+API_EINVAL = -1                 # RR_API_EINVAL (rr_serdes.h)
 SNAPPY_STATUS = {0: "OK", 1: "HEADER", 2: "TRUNC", 3: "OFFSET", 4: "OVERFLOW", 5: "LENGTH", 6: "CAPACITY"}
 LZ4_STATUS = dict(SNAPPY_STATUS)   # RR_LZ4_* parallel RR_SNAPPY_*
 
@@ -196,6 +214,11 @@ def lib():
         L.rr_rdbsave_batch.argtypes = [vp, C.POINTER(FlatBatch), C.POINTER(BlobBatch), vp, vp, vp, C.POINTER(RdbSaveOpts), vp]
         L.rr_rdbsave_batch_host.argtypes = [vp, vp, vp, u64, vp, u64, u64, C.POINTER(RdbSaveOpts), vp, u64, vp, vp, vp,
                                             C.POINTER(Totals)]
+    if "RR_LIB" not in os.environ or hasattr(L, "rr_rdbload_batch"):   # (RR_LIB: an older build may predate them)
+        L.rr_rdbload_bound.argtypes = [u64, u64]
+        L.rr_rdbload_bound.restype = u64
+        L.rr_rdbload_batch.argtypes = [vp, C.POINTER(BlobBatch), vp, C.POINTER(BlobBatch), vp, vp, C.POINTER(RdbLoadOpts), vp]
+        L.rr_rdbload_batch_host.argtypes = [vp, vp, vp, vp, u64, C.POINTER(RdbLoadOpts), vp, u64, vp, vp, C.POINTER(Totals)]
     if hasattr(L, "rr_host_decode_batch"):   # (RR_LIB: an older build for A/B timing may predate it)
         L.rr_host_reserve.argtypes = [vp, u64]
         L.rr_host_reserve.restype = u64
@@ -614,6 +637,38 @@ class Engine:
                                         C.c_void_p(status.data_ptr()), C.c_void_p(totals.data_ptr()), C.byref(opts),
                                         _sp(stream)))
 
+    # ---- RDB value payloads -> rock blobs (include/rr_rdbload.h) --------------------------------
+    def rdbload_host(self, data: np.ndarray, offsets: np.ndarray, types: np.ndarray, opts: RdbLoadOpts | None = None,
+                     out_cap: int | None = None):
+        """RDB payloads -> (blob data, offsets, status, totals): the blob desObject turns into the object
+        rdbLoadObject builds.  out_cap None: asks for the size first (a call with out_cap 0)."""
+        n = len(offsets) - 1
+        data = np.ascontiguousarray(data, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        types = np.ascontiguousarray(types, np.uint8)
+        out_offsets = np.zeros(n + 1, np.uint64)
+        status = np.zeros(max(n, 1), np.uint8)
+        t = Totals()
+        po = C.byref(opts) if opts is not None else None
+        if out_cap is None:
+            _check(self._L.rr_rdbload_batch_host(self._ctx, _ptr(data), _ptr(offsets), _ptr(types), n, po, None, 0,
+                                                 _ptr(out_offsets), _ptr(status), C.byref(t)))
+            out_cap = int(out_offsets[-1])
+        out = np.zeros(max(out_cap, 1), np.uint8)
+        _check(self._L.rr_rdbload_batch_host(self._ctx, _ptr(data), _ptr(offsets), _ptr(types), n, po, _ptr(out), out_cap,
+                                             _ptr(out_offsets), _ptr(status), C.byref(t)))
+        return out[:min(int(out_offsets[-1]), out_cap)], out_offsets, status[:n], t.as_dict()
+
+    def rdbload(self, data, offsets, types, out_data, out_offsets, status, totals, opts: RdbLoadOpts | None = None,
+                stream=None):
+        """rr_rdbload_batch on torch CUDA tensors; no host sync.  out_data may be empty (sizes only)."""
+        n = out_offsets.numel() - 1
+        inb = BlobBatch(data.data_ptr() if data.numel() else None, offsets.data_ptr(), n, data.numel())
+        outb = BlobBatch(out_data.data_ptr() if out_data.numel() else None, out_offsets.data_ptr(), n, out_data.numel())
+        _check(self._L.rr_rdbload_batch(self._ctx, C.byref(inb), C.c_void_p(types.data_ptr()), C.byref(outb),
+                                        C.c_void_p(status.data_ptr()), C.c_void_p(totals.data_ptr()),
+                                        C.byref(opts) if opts is not None else None, _sp(stream)))
+
     def encode_device(self, values, elems, arena, out_data, out_offsets, totals, stream=None):
         n = out_offsets.numel() - 1
         inb = FlatBatch(values.data_ptr(), elems.data_ptr(), arena.data_ptr(), n, elems.numel() // 16,
@@ -688,3 +743,8 @@ def rdbsave_bound(values: np.ndarray, elems: np.ndarray) -> int:
     """rr_rdbsave_bound of a flat batch: an upper bound on the bytes rdbsave writes for it."""
     pay = int(elems["len"][(elems["kind"] == K_STR) | (elems["kind"] == K_ZLRAW)].astype(np.uint64).sum())
     return int(lib().rr_rdbsave_bound(len(values), len(elems), pay))
+
+
+def rdbload_bound(n: int, payload_bytes: int) -> int:
+    """rr_rdbload_bound: an upper bound on the blob bytes of n payloads without LZF strings."""
+    return int(lib().rr_rdbload_bound(n, payload_bytes))

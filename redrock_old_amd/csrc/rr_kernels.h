@@ -63,6 +63,12 @@ uint64_t rr_rdbsave_scratch_words(uint64_t n, uint64_t lzf_elems);
 hipError_t rr_launch_rdbsave(const rr_value *values, const rr_elem *elems, uint64_t elem_cap, const uint8_t *arena,
                              uint64_t arena_cap, uint64_t n, int list_fill, int lzf, uint8_t *out, uint64_t cap, uint64_t *offsets,
                              uint8_t *types, uint8_t *status, uint64_t *scratch, rr_totals *totals, hipStream_t stream);
+/* rr_rdbload.hip (include/rr_rdbload.h): sizes, scan, emit; scratch of rr_rdbload_scratch_words(n).
+ * opt6: lru & RR_LRU_MASK, then the five thresholds in rr_rdbload_opts' order */
+uint64_t rr_rdbload_scratch_words(uint64_t n);
+hipError_t rr_launch_rdbload(const uint8_t *data, uint64_t in_cap, const uint64_t *in_offs, const uint8_t *types, uint64_t n,
+                             const uint32_t *opt6, uint8_t *out, uint64_t out_cap, uint64_t *out_offs, uint8_t *status,
+                             uint64_t *scratch, rr_totals *totals, hipStream_t stream);
 hipError_t rr_launch_shard_plan(const uint64_t *offsets, uint64_t n, uint32_t g, uint64_t *plan, hipStream_t stream);
 hipError_t rr_launch_offsets_rebase(uint64_t *offs, uint64_t count, uint64_t sub, hipStream_t stream);
 hipError_t rr_launch_flat_rebase(rr_value *values, uint64_t n, rr_elem *elems, uint64_t ne, uint64_t elem_add,
