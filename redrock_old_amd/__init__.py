@@ -77,6 +77,24 @@ class RdbLoadOpts(C.Structure):
                          zset_max_ziplist_entries, zset_max_ziplist_value, flags)
 
 
+class RdbFileIn(C.Structure):
+    """rr_rdbfile_in (include/rr_rdbfile.h): device pointers for rr_rdbfile_section, host ones for _host."""
+    _fields_ = [("payloads", BlobBatch), ("keys", BlobBatch), ("types", C.c_void_p), ("status", C.c_void_p),
+                ("expires", C.c_void_p), ("idle", C.c_void_p), ("freq", C.c_void_p), ("head", C.c_void_p),
+                ("head_bytes", C.c_uint64)]
+
+
+class RdbFileResult(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("n_bad", C.c_uint64), ("status", C.c_uint32), ("rsv", C.c_uint32)]
+
+    def as_dict(self):
+        return {"bytes": int(self.bytes), "n_bad": int(self.n_bad), "status": int(self.status)}
+
+
+class RdbFileRepl(C.Structure):
+    _fields_ = [("stream_db", C.c_int32), ("replid", C.c_char_p), ("offset", C.c_int64)]
+
+
 class Shard(C.Structure):
     _fields_ = [("v0", C.c_uint64), ("v1", C.c_uint64), ("b0", C.c_uint64), ("b1", C.c_uint64)]
 
@@ -129,6 +147,15 @@ RDBLOAD_EXPORTS = ["rr_rdbload_bound", "rr_rdbload_batch", "rr_rdbload_batch_hos
 RDBLOAD_E_TYPE, RDBLOAD_E_LEN, RDBLOAD_E_TRUNC, RDBLOAD_E_LZF = 32, 33, 34, 35
 RDBLOAD_E_EXTRA, RDBLOAD_E_ZIPLIST, RDBLOAD_E_CONVERT = 36, 37, 38
 RDBLOAD_LZF_NODE_MAX = 10240    # the longest List node taken in the LZF form
+# include/rr_rdbfile.h (RDB stream framing, DUMP payloads and their CRC-64 around the payloads above)
+RDBFILE_EXPORTS = ["rr_rdbfile_bound", "rr_rdbfile_section", "rr_rdbfile_section_host", "rr_crc64_device",
+                   "rr_rdbdump_batch", "rr_rdbdump_batch_host", "rr_rdbdump_verify_batch", "rr_rdbdump_verify_batch_host",
+                   "rr_rdbfile_head", "rr_rdbfile_selectdb", "rr_crc64", "rr_crc64_shift", "rr_crc64_mul"]
+RDBFILE_IDLE, RDBFILE_FREQ, RDBFILE_EOF, RDBFILE_NO_CKSUM = 1, 2, 4, 8
+RDBFILE_E_VALUE, RDBFILE_E_KEY, RDBDUMP_E_SHORT, RDBDUMP_E_VERSION, RDBDUMP_E_CRC = 40, 41, 42, 43, 44
+# the CRC kernels' shape (rr_rdbfile.h): bytes a lane, bytes a wave and step, waves a launch at most
+CRC64_RUN, CRC64_PIECE, CRC64_MAX_WAVES = 256, 64 * 256, 2048
+RDBDUMP_MAX_WAVES = 16384       # rr_rdbdump_batch / rr_rdbdump_verify_batch: a wave a value
 API_EINVAL = -1                 # RR_API_EINVAL (rr_serdes.h)
 SNAPPY_STATUS = {0: "OK", 1: "HEADER", 2: "TRUNC", 3: "OFFSET", 4: "OVERFLOW", 5: "LENGTH", 6: "CAPACITY"}
 LZ4_STATUS = dict(SNAPPY_STATUS)   # RR_LZ4_* parallel RR_SNAPPY_*
@@ -219,6 +246,27 @@ def lib():
         L.rr_rdbload_bound.restype = u64
         L.rr_rdbload_batch.argtypes = [vp, C.POINTER(BlobBatch), vp, C.POINTER(BlobBatch), vp, vp, C.POINTER(RdbLoadOpts), vp]
         L.rr_rdbload_batch_host.argtypes = [vp, vp, vp, vp, u64, C.POINTER(RdbLoadOpts), vp, u64, vp, vp, C.POINTER(Totals)]
+    if "RR_LIB" not in os.environ or hasattr(L, "rr_rdbfile_section"):   # (RR_LIB: an older build may predate them)
+        L.rr_rdbfile_bound.argtypes = [u64, u64, u64, u64]
+        L.rr_rdbfile_bound.restype = u64
+        L.rr_rdbfile_section.argtypes = [vp, C.POINTER(RdbFileIn), C.c_uint32, vp, u64, vp, vp, vp, vp, vp]
+        L.rr_rdbfile_section_host.argtypes = [vp, C.POINTER(RdbFileIn), C.c_uint32, vp, u64, vp, vp, vp,
+                                              C.POINTER(RdbFileResult)]
+        L.rr_crc64_device.argtypes = [vp, vp, u64, vp, vp]
+        L.rr_rdbdump_batch.argtypes = [vp, C.POINTER(BlobBatch), vp, vp, C.POINTER(BlobBatch), vp, vp, vp]
+        L.rr_rdbdump_batch_host.argtypes = [vp, vp, vp, vp, vp, u64, vp, u64, vp, vp, C.POINTER(RdbFileResult)]
+        L.rr_rdbdump_verify_batch.argtypes = [vp, C.POINTER(BlobBatch), C.POINTER(BlobBatch), vp, vp, vp, vp]
+        L.rr_rdbdump_verify_batch_host.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, vp, C.POINTER(RdbFileResult)]
+        L.rr_rdbfile_head.argtypes = [vp, u64, C.c_char_p, C.c_int64, u64, C.POINTER(RdbFileRepl), C.c_int]
+        L.rr_rdbfile_head.restype = u64
+        L.rr_rdbfile_selectdb.argtypes = [vp, u64, u64, u64, u64]
+        L.rr_rdbfile_selectdb.restype = u64
+        L.rr_crc64.argtypes = [u64, vp, u64]
+        L.rr_crc64.restype = u64
+        L.rr_crc64_shift.argtypes = [u64, u64]
+        L.rr_crc64_shift.restype = u64
+        L.rr_crc64_mul.argtypes = [u64, u64]
+        L.rr_crc64_mul.restype = u64
     if hasattr(L, "rr_host_decode_batch"):   # (RR_LIB: an older build for A/B timing may predate it)
         L.rr_host_reserve.argtypes = [vp, u64]
         L.rr_host_reserve.restype = u64
@@ -669,6 +717,98 @@ class Engine:
                                         C.c_void_p(status.data_ptr()), C.c_void_p(totals.data_ptr()),
                                         C.byref(opts) if opts is not None else None, _sp(stream)))
 
+    # ---- RDB streams and DUMP payloads with their CRC-64 (include/rr_rdbfile.h) -------------------
+    def rdbfile_section(self, pay_data, pay_offsets, types, status, key_data, key_offsets, out, rec_offsets, rec_status,
+                        state, result, expires=None, idle=None, freq=None, head=None, flags: int = 0, stream=None,
+                        out_cap: int | None = None, key_cap: int | None = None, pay_cap: int | None = None):
+        """rr_rdbfile_section on torch CUDA tensors; no host sync.  state: int64[2] (checksum in and out,
+        section bytes), result: uint8[24] (rr_rdbfile_result).  *_cap default to the tensors' sizes."""
+        n = _n_offsets(pay_offsets)
+        dp = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        arg = RdbFileIn(BlobBatch(dp(pay_data), pay_offsets.data_ptr(), n, pay_data.numel() if pay_cap is None else pay_cap),
+                        BlobBatch(dp(key_data), key_offsets.data_ptr(), n, key_data.numel() if key_cap is None else key_cap),
+                        dp(types), dp(status), dp(expires), dp(idle), dp(freq), dp(head),
+                        head.numel() if head is not None else 0)
+        _check(self._L.rr_rdbfile_section(self._ctx, C.byref(arg), flags, dp(out), out.numel() if out_cap is None else out_cap,
+                                          rec_offsets.data_ptr(), dp(rec_status), state.data_ptr(), result.data_ptr(),
+                                          _sp(stream)))
+
+    def rdbfile_section_host(self, pay_data, pay_offsets, types, status, key_data, key_offsets, expires=None, idle=None,
+                             freq=None, head: bytes = b"", flags: int = 0, crc_in: int = 0, out_cap: int | None = None):
+        """rr_rdbfile_section_host over numpy arrays: (section bytes, rec_offsets, rec_status, checksum out,
+        result dict).  out_cap None: rr_rdbfile_bound."""
+        n = len(pay_offsets) - 1
+        pay_data, key_data = np.ascontiguousarray(pay_data, np.uint8), np.ascontiguousarray(key_data, np.uint8)
+        pay_offsets, key_offsets = np.ascontiguousarray(pay_offsets, np.uint64), np.ascontiguousarray(key_offsets, np.uint64)
+        types, status = np.ascontiguousarray(types, np.uint8), np.ascontiguousarray(status, np.uint8)
+        expires = None if expires is None else np.ascontiguousarray(expires, np.int64)
+        idle = None if idle is None else np.ascontiguousarray(idle, np.uint64)
+        freq = None if freq is None else np.ascontiguousarray(freq, np.uint8)
+        hd = np.frombuffer(bytes(head), np.uint8)
+        if out_cap is None:
+            out_cap = rdbfile_bound(n, key_data.size, pay_data.size, len(hd))
+        out = np.zeros(max(out_cap, 1), np.uint8)
+        ro, rs = np.zeros(n + 1, np.uint64), np.zeros(max(n, 1), np.uint8)
+        st = np.array([crc_in, 0], np.uint64)
+        res = RdbFileResult()
+        arg = RdbFileIn(BlobBatch(_ptr(pay_data), _ptr(pay_offsets), n, pay_data.size),
+                        BlobBatch(_ptr(key_data), _ptr(key_offsets), n, key_data.size), _ptr(types), _ptr(status),
+                        _ptr(expires), _ptr(idle), _ptr(freq), _ptr(hd), len(hd))
+        _check(self._L.rr_rdbfile_section_host(self._ctx, C.byref(arg), flags, _ptr(out), out_cap, _ptr(ro), _ptr(rs),
+                                               _ptr(st), C.byref(res)))
+        nb = int(res.bytes) if res.status == 0 else 0
+        return out[:nb], ro, rs[:n], int(st[0]), res.as_dict()
+
+    def crc64_device(self, data, nbytes: int, state, stream=None):
+        """state[0] = crc64(state[0], data[:nbytes]) on the device (torch CUDA tensors; state int64[2])."""
+        _check(self._L.rr_crc64_device(self._ctx, data.data_ptr() if nbytes else None, nbytes, state.data_ptr(), _sp(stream)))
+
+    def rdbdump(self, data, offsets, types, status, out, out_offsets, out_status, result, stream=None,
+                out_cap: int | None = None):
+        """rr_rdbdump_batch on torch CUDA tensors; no host sync."""
+        n = _n_offsets(offsets)
+        dp = lambda t: t.data_ptr() if t.numel() else None
+        inb = BlobBatch(dp(data), offsets.data_ptr(), n, data.numel())
+        outb = BlobBatch(dp(out), out_offsets.data_ptr(), n, out.numel() if out_cap is None else out_cap)
+        _check(self._L.rr_rdbdump_batch(self._ctx, C.byref(inb), dp(types), dp(status), C.byref(outb), dp(out_status),
+                                        result.data_ptr(), _sp(stream)))
+
+    def rdbdump_host(self, data, offsets, types, status, out_cap: int | None = None):
+        """Payloads -> (DUMP bytes, offsets, status, result dict)."""
+        n = len(offsets) - 1
+        data, offsets = np.ascontiguousarray(data, np.uint8), np.ascontiguousarray(offsets, np.uint64)
+        types, status = np.ascontiguousarray(types, np.uint8), np.ascontiguousarray(status, np.uint8)
+        if out_cap is None:
+            out_cap = data.size + 11 * n
+        out = np.zeros(max(out_cap, 1), np.uint8)
+        oo, os_ = np.zeros(n + 1, np.uint64), np.zeros(max(n, 1), np.uint8)
+        res = RdbFileResult()
+        _check(self._L.rr_rdbdump_batch_host(self._ctx, _ptr(data), _ptr(offsets), _ptr(types), _ptr(status), n, _ptr(out),
+                                             out_cap, _ptr(oo), _ptr(os_), C.byref(res)))
+        return out[:min(int(oo[-1]), out_cap)], oo, os_[:n], res.as_dict()
+
+    def rdbdump_verify(self, data, offsets, out, out_offsets, types, status, result, stream=None):
+        """rr_rdbdump_verify_batch on torch CUDA tensors; no host sync.  out may be empty (sizes only)."""
+        n = _n_offsets(offsets)
+        dp = lambda t: t.data_ptr() if t.numel() else None
+        inb = BlobBatch(dp(data), offsets.data_ptr(), n, data.numel())
+        outb = BlobBatch(dp(out), out_offsets.data_ptr(), n, out.numel())
+        _check(self._L.rr_rdbdump_verify_batch(self._ctx, C.byref(inb), C.byref(outb), dp(types), dp(status),
+                                               result.data_ptr(), _sp(stream)))
+
+    def rdbdump_verify_host(self, data, offsets, out_cap: int | None = None):
+        """DUMP payloads -> (payload bytes, offsets, types, status, result dict)."""
+        n = len(offsets) - 1
+        data, offsets = np.ascontiguousarray(data, np.uint8), np.ascontiguousarray(offsets, np.uint64)
+        if out_cap is None:
+            out_cap = data.size
+        out = np.zeros(max(out_cap, 1), np.uint8)
+        oo, ty, st = np.zeros(n + 1, np.uint64), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+        res = RdbFileResult()
+        _check(self._L.rr_rdbdump_verify_batch_host(self._ctx, _ptr(data), _ptr(offsets), n, _ptr(out), out_cap, _ptr(oo),
+                                                    _ptr(ty), _ptr(st), C.byref(res)))
+        return out[:min(int(oo[-1]), out_cap)], oo, ty[:n], st[:n], res.as_dict()
+
     def encode_device(self, values, elems, arena, out_data, out_offsets, totals, stream=None):
         n = out_offsets.numel() - 1
         inb = FlatBatch(values.data_ptr(), elems.data_ptr(), arena.data_ptr(), n, elems.numel() // 16,
@@ -729,6 +869,11 @@ class Comm:
         _check(self._L.rr_gather(self._c, C.byref(mine), mine_elems, plan, root, C.byref(whole), _sp(stream)))
 
 
+def _n_offsets(t) -> int:
+    """The values of an offsets tensor of n + 1 u64 words, whatever dtype it is viewed as."""
+    return t.numel() * t.element_size() // 8 - 1
+
+
 def _sp(stream):
     return C.c_void_p(stream.cuda_stream) if stream is not None else None
 
@@ -748,3 +893,39 @@ def rdbsave_bound(values: np.ndarray, elems: np.ndarray) -> int:
 def rdbload_bound(n: int, payload_bytes: int) -> int:
     """rr_rdbload_bound: an upper bound on the blob bytes of n payloads without LZF strings."""
     return int(lib().rr_rdbload_bound(n, payload_bytes))
+
+
+# ---- include/rr_rdbfile.h: the host helpers (no GPU) ---------------------------------------------
+def crc64(crc: int, data) -> int:
+    """rr_crc64: crc64.c's crc64() over tables generated from the polynomial."""
+    b = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+    return int(lib().rr_crc64(crc, _ptr(b), b.size))
+
+
+def crc64_shift(crc: int, n: int) -> int:
+    """rr_crc64_shift: crc * x^(8n) mod P, the checksum after n more zero bytes."""
+    return int(lib().rr_crc64_shift(crc, n))
+
+
+def rdbfile_bound(n: int, key_bytes: int, payload_bytes: int, head_bytes: int = 0) -> int:
+    return int(lib().rr_rdbfile_bound(n, key_bytes, payload_bytes, head_bytes))
+
+
+def rdbfile_head(ver: str, ctime: int, used_mem: int, repl=None, aof_preamble: bool = False, cap: int | None = None):
+    """rr_rdbfile_head: "REDIS0009" and the aux fields; repl: None or (stream_db, replid, offset).
+    cap None: the size first.  Returns (bytes needed, the buffer of cap bytes as the call left it)."""
+    r = RdbFileRepl(repl[0], repl[1].encode(), repl[2]) if repl is not None else None
+    pr = C.byref(r) if r is not None else None
+    L = lib()
+    if cap is None:
+        cap = int(L.rr_rdbfile_head(None, 0, ver.encode(), ctime, used_mem, pr, int(aof_preamble)))
+    buf = np.full(max(cap, 1), 0xA5, np.uint8)
+    need = int(L.rr_rdbfile_head(_ptr(buf), cap, ver.encode(), ctime, used_mem, pr, int(aof_preamble)))
+    return need, buf[:cap].tobytes()
+
+
+def rdbfile_selectdb(dbid: int, db_size: int, expires_size: int, cap: int = 32):
+    """rr_rdbfile_selectdb: (bytes needed, the buffer of cap bytes as the call left it)."""
+    buf = np.full(max(cap, 1), 0xA5, np.uint8)
+    need = int(lib().rr_rdbfile_selectdb(_ptr(buf), cap, dbid, db_size, expires_size))
+    return need, buf[:cap].tobytes()

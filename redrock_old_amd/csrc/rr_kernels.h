@@ -69,6 +69,27 @@ uint64_t rr_rdbload_scratch_words(uint64_t n);
 hipError_t rr_launch_rdbload(const uint8_t *data, uint64_t in_cap, const uint64_t *in_offs, const uint8_t *types, uint64_t n,
                              const uint32_t *opt6, uint8_t *out, uint64_t out_cap, uint64_t *out_offs, uint8_t *status,
                              uint64_t *scratch, rr_totals *totals, hipStream_t stream);
+/* rr_rdbfile.hip (include/rr_rdbfile.h).  The CRC kernels' shape is RR_CRC64_RUN bytes a lane,
+ * RR_CRC64_PIECE bytes a wave and step, at most RR_CRC64_MAX_WAVES waves (rr_rdbfile.h, mirrored in
+ * the Python binding).  The section: sizes, scan, emit, CRC, combine; every pointer of *in on the
+ * device, scratch of rr_rdbfile_scratch_words(n).  rr_launch_crc64: state[0] = crc64(state[0],
+ * data[0, bytes)), scratch of rr_crc64_scratch_words().  The DUMP calls: sizes / check, scan, emit /
+ * copy; scratch of rr_rdbdump_scratch_words(n). */
+struct rr_rdbfile_in;
+struct rr_rdbfile_result;
+uint64_t rr_rdbfile_scratch_words(uint64_t n);
+uint64_t rr_crc64_scratch_words(void);
+uint64_t rr_rdbdump_scratch_words(uint64_t n);
+hipError_t rr_launch_rdbfile(const struct rr_rdbfile_in *in, uint32_t flags, uint8_t *out, uint64_t out_cap, uint64_t *rec_offsets,
+                             uint8_t *rec_status, uint64_t *state, struct rr_rdbfile_result *result, uint64_t *scratch,
+                             hipStream_t stream);
+hipError_t rr_launch_crc64(const uint8_t *data, uint64_t bytes, uint64_t *state, uint64_t *scratch, hipStream_t stream);
+hipError_t rr_launch_rdbdump(const uint8_t *data, uint64_t in_cap, const uint64_t *in_offs, const uint8_t *types,
+                             const uint8_t *status, uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *out_offs,
+                             uint8_t *out_status, uint64_t *scratch, struct rr_rdbfile_result *result, hipStream_t stream);
+hipError_t rr_launch_rdbdump_verify(const uint8_t *data, uint64_t in_cap, const uint64_t *in_offs, uint64_t n, uint8_t *out,
+                                    uint64_t out_cap, uint64_t *out_offs, uint8_t *types, uint8_t *status, uint64_t *scratch,
+                                    struct rr_rdbfile_result *result, hipStream_t stream);
 hipError_t rr_launch_shard_plan(const uint64_t *offsets, uint64_t n, uint32_t g, uint64_t *plan, hipStream_t stream);
 hipError_t rr_launch_offsets_rebase(uint64_t *offs, uint64_t count, uint64_t sub, hipStream_t stream);
 hipError_t rr_launch_flat_rebase(rr_value *values, uint64_t n, rr_elem *elems, uint64_t ne, uint64_t elem_add,
