@@ -5,12 +5,14 @@
  * (a hipMemsetAsync of the look-back words + one kernel, no host sync) and host-pointer
  * variants that stage through pinned buffers and the context's device buffers.
  */
+#include <errno.h>
 #include <sched.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
+#include <unistd.h>
 
 #include "rr_internal.h"
 
@@ -26,7 +28,6 @@ int rr_fail(int code, const char *fmt, ...) {
 #define fail rr_fail
 #define ensure_scratch rr_ensure_scratch
 #define mark_scratch rr_mark_scratch
-#define dgrow rr_dgrow
 
 int rr_ctx_create(int device, rr_ctx **out) {
     if (!out) return fail(RR_API_EINVAL, "out is NULL");
@@ -315,7 +316,54 @@ int rr_dgrow(void **p, size_t *cap, size_t need) {
     *cap = want;
     return RR_API_OK;
 }
-#define GROW(P, C, N) do { int r_ = dgrow((void **)&(P), &(C), (N)); if (r_) return r_; } while (0)
+
+/* ---- shared by the host files (rr_internal.h) ---------------------------------------------- */
+uint64_t rr_reach(const uint64_t *offs, uint64_t n, uint64_t cap) {
+    uint64_t m = 0;
+    for (uint64_t i = 0; i <= n; i++)
+        if (offs[i] > m && offs[i] <= cap) m = offs[i];
+    return m;
+}
+
+int rr_check_blob_io(const rr_ctx *c, const rr_blob_batch *in, const rr_blob_batch *out, const void *d_result, int have_arrays) {
+    if (!c || !in || !out || !d_result) return fail(RR_API_EINVAL, "NULL argument");
+    if (out->n != in->n) return fail(RR_API_EINVAL, "out->n != in->n");
+    if (in->n >= RR_MAX_VALUES) return fail(RR_API_EINVAL, "batch too large (value indices are 32-bit)");
+    if (!in->offsets || !out->offsets) return fail(RR_API_EINVAL, "NULL offsets");
+    if (in->n && !have_arrays) return fail(RR_API_EINVAL, "NULL buffer");
+    if ((in->data_cap && !in->data) || (out->data_cap && !out->data)) return fail(RR_API_EINVAL, "NULL buffer");
+    return RR_API_OK;
+}
+
+int rr_host_finish(rr_ctx *c, const char *name, const uint64_t *bytes, void *out, const void *d_out, uint64_t cap) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (*bytes == ~0ull) return fail(RR_API_EDEVICE, "%s: device-side failure (look-back timeout)", name);
+    DOWN(out, d_out, *bytes < cap ? *bytes : cap);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return RR_API_OK;
+}
+
+int rr_read_full(int fd, void *buf, size_t len) {
+    char *p = (char *)buf;
+    while (len) {
+        ssize_t r = read(fd, p, len);
+        if (r == 0) return 0;
+        if (r < 0) { if (errno == EINTR) continue; return -1; }
+        p += r;
+        len -= (size_t)r;
+    }
+    return 1;
+}
+int rr_write_full(int fd, const void *buf, size_t len) {
+    const char *p = (const char *)buf;
+    while (len) {
+        ssize_t r = write(fd, p, len);
+        if (r < 0) { if (errno == EINTR) continue; return -1; }
+        p += r;
+        len -= (size_t)r;
+    }
+    return 1;
+}
 
 /* ---- pipelined host decode -------------------------------------------------------------
  * A batch of more than one RR_HOST_CHUNK goes in chunks of whole values (at most
@@ -547,21 +595,21 @@ int rr_decode_batch_host(rr_ctx *c, const uint8_t *data, const uint64_t *offsets
         }
     }
     HIPCHK(hipMemsetAsync(c->d_in, 0, pbytes + 16, c->stream));
-    if (bytes) HIPCHK(hipMemcpyAsync(c->d_in, data, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    UP(c->d_in, data, bytes);
+    UP(c->d_off, offsets, (n + 1) * sizeof(uint64_t));
     HIPCHK(hipMemsetAsync(c->d_arena, 0, pbytes ? pbytes : 16, c->stream));
     rr_blob_batch in = {(uint8_t *)c->d_in, (uint64_t *)c->d_off, n, pbytes};
     rr_flat_batch out = {(rr_value *)c->d_vals, (rr_elem *)c->d_elems, (uint8_t *)c->d_arena, n, elem_cap, pbytes};
     int rc = rr_decode_batch(c, &in, &out, c->d_totals, c->stream);
     if (rc) return rc;
     rr_totals t;
-    HIPCHK(hipMemcpyAsync(&t, c->d_totals, sizeof t, hipMemcpyDeviceToHost, c->stream));
+    DOWN(&t, c->d_totals, sizeof t);
     HIPCHK(hipStreamSynchronize(c->stream));
     if (t.bytes == ~0ull) return fail(RR_API_EDEVICE, "decode: device-side failure (look-back timeout)");
-    if (n) HIPCHK(hipMemcpyAsync(values, c->d_vals, n * sizeof(rr_value), hipMemcpyDeviceToHost, c->stream));
+    DOWN(values, c->d_vals, n * sizeof(rr_value));
     uint64_t ne = t.n_elems < elem_cap ? t.n_elems : elem_cap;
-    if (ne && elems) HIPCHK(hipMemcpyAsync(elems, c->d_elems, ne * sizeof(rr_elem), hipMemcpyDeviceToHost, c->stream));
-    if (bytes && arena) HIPCHK(hipMemcpyAsync(arena, c->d_arena, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (elems) DOWN(elems, c->d_elems, ne * sizeof(rr_elem));
+    if (arena) DOWN(arena, c->d_arena, bytes);
     HIPCHK(hipStreamSynchronize(c->stream));
     if (n == 0) memset(&t, 0, sizeof t);
     if (totals) *totals = t;
@@ -738,21 +786,18 @@ int rr_encode_batch_host(rr_ctx *c, const rr_value *values, const rr_elem *elems
     GROW(c->d_ooff, c->c_ooff, (n + 1) * sizeof(uint64_t));
     if (n > 1 && n * sizeof(rr_value) + n_elems * sizeof(rr_elem) + arena_bytes > RR_HOST_CHUNK)
         return encode_host_pipelined(c, values, elems, n_elems, arena, arena_bytes, n, data, data_cap, offsets, totals);
-    if (n) HIPCHK(hipMemcpyAsync(c->d_vals, values, n * sizeof(rr_value), hipMemcpyHostToDevice, c->stream));
-    if (n_elems) HIPCHK(hipMemcpyAsync(c->d_elems, elems, n_elems * sizeof(rr_elem), hipMemcpyHostToDevice, c->stream));
-    if (arena_bytes) HIPCHK(hipMemcpyAsync(c->d_arena, arena, arena_bytes, hipMemcpyHostToDevice, c->stream));
+    UP(c->d_vals, values, n * sizeof(rr_value));
+    UP(c->d_elems, elems, n_elems * sizeof(rr_elem));
+    UP(c->d_arena, arena, arena_bytes);
     rr_flat_batch in = {(rr_value *)c->d_vals, (rr_elem *)c->d_elems, (uint8_t *)c->d_arena, n, n_elems, arena_bytes};
     rr_blob_batch out = {(uint8_t *)c->d_out, (uint64_t *)c->d_ooff, n, data_cap};
     int rc = rr_encode_batch(c, &in, &out, c->d_totals, c->stream);
     if (rc) return rc;
     rr_totals t;
-    HIPCHK(hipMemcpyAsync(&t, c->d_totals, sizeof t, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(offsets, c->d_ooff, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (t.bytes == ~0ull) return fail(RR_API_EDEVICE, "encode: device-side failure (look-back timeout)");
-    uint64_t nb = t.bytes < data_cap ? t.bytes : data_cap;
-    if (nb) HIPCHK(hipMemcpyAsync(data, c->d_out, nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    DOWN(&t, c->d_totals, sizeof t);
+    DOWN(offsets, c->d_ooff, (n + 1) * sizeof(uint64_t));
+    rc = rr_host_finish(c, "encode", &t.bytes, data, c->d_out, data_cap);
+    if (rc) return rc;
     if (n == 0) memset(&t, 0, sizeof t);
     if (totals) *totals = t;
     return RR_API_OK;

@@ -1,6 +1,7 @@
 // rr_device.h — device-side building blocks shared by the decode and encode kernels:
 // unaligned little-endian loads, strict integer parse / decimal render (util.c, sds.c),
-// wave64 scans and the decoupled look-back used for output offsets.
+// cross-lane reads, buffer resources, the whole-wave copy, wave64 scans and the decoupled look-back
+// used for output offsets.  Shared by every kernel file of the engine.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -83,6 +84,64 @@ __device__ __forceinline__ uint32_t dec_write(uint8_t *d, int64_t value) {
 }
 
 __device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }
+
+// a lane's value (k wave-uniform) / the first active lane's, in every lane
+__device__ __forceinline__ uint32_t rl32(uint32_t x, uint32_t k) { return (uint32_t)__builtin_amdgcn_readlane((int)x, (int)k); }
+__device__ __forceinline__ uint64_t rl64(uint64_t x, uint32_t k) { return (uint64_t)rl32((uint32_t)x, k) | ((uint64_t)rl32((uint32_t)(x >> 32), k) << 32); }
+__device__ __forceinline__ uint32_t rfl(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+__device__ __forceinline__ uint64_t first64(uint64_t x) { return (uint64_t)rfl((uint32_t)x) | ((uint64_t)rfl((uint32_t)(x >> 32)) << 32); }
+
+// the wave's earlier stores have reached the L2 (before it reads its own output back)
+__device__ __forceinline__ void wait_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// LDS pointers kept in address space 3, so accesses compile to ds_* (a generic pointer gives flat_*
+// instructions, whose waits also drain every outstanding global store of the wave)
+typedef __attribute__((address_space(3))) uint8_t lds_u8;
+typedef __attribute__((address_space(3))) uint16_t lds_u16;
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
+typedef __attribute__((address_space(3))) uint64_t lds_u64;
+
+// Buffer resources (wave-uniform arguments): loads past `bytes` read zeros, stores past it are
+// dropped.  mk_rsrc covers exactly `bytes`; mk_rsrc_clamped takes a 64-bit size and covers at most
+// a resource's reach.
+typedef __amdgpu_buffer_rsrc_t rsrc_t;
+__device__ __forceinline__ rsrc_t mk_rsrc(const void *base, uint32_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ rsrc_t mk_rsrc_clamped(const void *base, uint64_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)(bytes < 0x7FFFFFF0ull ? bytes : 0x7FFFFFF0ull),
+                                             0x00020000);
+}
+__device__ __forceinline__ uint32_t ld8(rsrc_t R, uint32_t k) { return __builtin_amdgcn_raw_buffer_load_b8(R, (int)k, 0, 0); }
+
+// the whole wave copies len bytes (wave-uniform arguments): bytes up to dst's 16-byte boundary, then
+// 16 bytes a lane (unaligned loads inside [src, src + len), aligned stores), then the tail bytes
+struct __attribute__((packed, aligned(1))) u128_ua { uint32_t a, b, c, d; };
+__device__ __forceinline__ void wave_copy(uint8_t *dst, const uint8_t *__restrict__ src, uint32_t len) {
+    const uint32_t lane = lane_id();
+    uint32_t head = (uint32_t)(0 - (uintptr_t)dst) & 15;
+    if (head > len) head = len;
+    if (lane < head) dst[lane] = src[lane];
+    const uint32_t body = (len - head) & ~15u;
+    dst += head;   // 16-byte aligned from here
+    src += head;
+    for (uint64_t k = (uint64_t)lane * 16; k < body; k += RR_WAVE * 16) {
+        const u128_ua x = *reinterpret_cast<const u128_ua *>(src + k);
+        *reinterpret_cast<uint4 *>(dst + k) = make_uint4(x.a, x.b, x.c, x.d);
+    }
+    if (lane < len - head - body) dst[body + lane] = src[body + lane];
+}
+// the bodies of the lanes with `mine` (each lane its own dst, src, len), one after the other by the
+// whole wave
+__device__ __forceinline__ void wave_copy_each(uint8_t *dst, const uint8_t *__restrict__ src, uint32_t len, bool mine) {
+    uint64_t m = __ballot(mine);
+    while (m) {
+        const uint32_t k = (uint32_t)__builtin_ctzll(m);
+        m &= m - 1;
+        wave_copy(reinterpret_cast<uint8_t *>(rl64((uint64_t)(uintptr_t)dst, k)),
+                  reinterpret_cast<const uint8_t *>(rl64((uint64_t)(uintptr_t)src, k)), rl32(len, k));
+    }
+}
 
 // Workgroup barrier that orders LDS only.  __syncthreads() is a workgroup-scope fence for all
 // memory: it makes every wave wait for the acknowledgement of its outstanding global stores

@@ -1,4 +1,4 @@
-/* rr_internal.h — what the C host files of the engine share (rr_api.c, rr_shard.c, rr_snappy_api.c). */
+/* rr_internal.h — what the C host files of the engine share; the function bodies are in rr_api.c. */
 #ifndef RR_INTERNAL_H
 #define RR_INTERNAL_H
 
@@ -56,5 +56,29 @@ int rr_dgrow(void **p, size_t *cap, size_t need);
 int rr_fail(int code, const char *fmt, ...);
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
     return rr_fail(RR_API_EHIP, "%s:%d %s: %s", __FILE__, __LINE__, #x, hipGetErrorString(e_)); } while (0)
+
+/* ---- what the host-pointer (*_host) entry points share; all of it returns from the caller on
+ * failure and stages on the context `c` in scope ---- */
+#define GROW(P, C, N) do { int r_ = rr_dgrow((void **)&(P), &(C), (N)); if (r_) return r_; } while (0)
+#define UP(D, S, B) do { if ((B) != 0) HIPCHK(hipMemcpyAsync((D), (S), (B), hipMemcpyHostToDevice, c->stream)); } while (0)
+#define DOWN(D, S, B) do { if ((B) != 0) HIPCHK(hipMemcpyAsync((D), (S), (B), hipMemcpyDeviceToHost, c->stream)); } while (0)
+
+#define RR_HIDDEN __attribute__((visibility("hidden")))   /* shared between the host files, not exported */
+
+/* the bytes the slices offs[0 .. n] reach within cap; a slice past them does not exist on the device */
+RR_HIDDEN uint64_t rr_reach(const uint64_t *offs, uint64_t n, uint64_t cap);
+/* The argument block of a device call from one blob batch to another (d_result: its rr_totals or
+ * rr_rdbfile_result; have_arrays: the call's per-value arrays are all there).  Sets the error. */
+RR_HIDDEN int rr_check_blob_io(const rr_ctx *c, const rr_blob_batch *in, const rr_blob_batch *out, const void *d_result,
+                               int have_arrays);
+/* The end of a *_host call whose result record (an rr_totals or an rr_rdbfile_result; *bytes its
+ * bytes field) and per-value arrays are already queued for download: waits for them, fails on the
+ * look-back's error mark, then brings down the first min(*bytes, cap) bytes of the output. */
+RR_HIDDEN int rr_host_finish(rr_ctx *c, const char *name, const uint64_t *bytes, void *out, const void *d_out, uint64_t cap);
+
+/* read / write exactly len bytes on a blocking fd: 1 done, 0 closed, -1 error
+ * (the reference's _read_pipe_by_length / _write_pipe_by_length, rock_rdb.c:64-103) */
+RR_HIDDEN int rr_read_full(int fd, void *buf, size_t len);
+RR_HIDDEN int rr_write_full(int fd, const void *buf, size_t len);
 
 #endif

@@ -32,12 +32,15 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "rr_device.h"
 #include "rr_kernels.h"
 #include "../../include/rr_lz4.h"
 
+using namespace rr;
+
 namespace {
 
-constexpr uint32_t WAVE = 64;
+constexpr uint32_t WAVE = RR_WAVE;
 // LDS window per wave of the decompressor (the block decompressed in place in it), as
 // rr_snappy.hip's: 18 KiB holds RocksDB's 16 KiB blocks plus a 2 KiB last entry, 8 waves per CU
 #ifndef RR_LZ4_DEC_WIN
@@ -57,23 +60,8 @@ constexpr uint32_t CHUNK = 1u << 16;   // positions a table entry can hold
 constexpr uint32_t MINMATCH = 4, LASTLITERALS = 5, MFLIMIT = 12, FASTLOOP = 64;   // lz4.c:189-195
 constexpr uint32_t BAIL = 0xFF;        // (internal) leave the LDS window for the global path
 
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
-typedef __attribute__((address_space(3))) uint16_t lds_u16;
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
 typedef __attribute__((address_space(3))) u32x4_t lds_u32x4;
-
-__device__ __forceinline__ rsrc_t mkr(const void *base, uint64_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)(bytes < 0x7FFFFFF0ull ? bytes : 0x7FFFFFF0ull),
-                                             0x00020000);
-}
-__device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }
-__device__ __forceinline__ uint32_t rdl(uint32_t v, uint32_t l) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
-}
-__device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ void wait_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // ---- decompression ------------------------------------------------------------------------
 
@@ -293,12 +281,12 @@ __global__ __launch_bounds__(WAVE) void lz4_dec_kernel(const uint8_t *__restrict
         const uint64_t base = c0 - s0;   // (whole dwords: the buffer's padding, not past it)
         const uint64_t span = (s0 + clen + 15) & ~15ull;
         uint8_t *gout = out + o0;
-        const rsrc_t Ro = mkr(gout, N);
+        const rsrc_t Ro = mk_rsrc_clamped(gout, N);
         uint32_t st = BAIL;
         if (N <= wcap && span <= wcap) {
             // stage: the block's 16-byte granules at the window's end (the allocation's last
             // 32 bytes: reads past the end), eight loads a lane in flight
-            const rsrc_t R = mkr(in + base, span < in_cap - base ? span : in_cap - base);
+            const rsrc_t R = mk_rsrc_clamped(in + base, span < in_cap - base ? span : in_cap - base);
             const uint32_t ng = (uint32_t)(span >> 4), D = wcap + 16 - 16 * ng;
             lds_u32x4 *d4 = (lds_u32x4 *)(win + D);
             for (uint32_t j0 = 0; j0 < ng; j0 += 8 * WAVE) {
@@ -324,7 +312,7 @@ __global__ __launch_bounds__(WAVE) void lz4_dec_kernel(const uint8_t *__restrict
             }
         }
         if (st == BAIL) {
-            GlobalMem m{mkr(in + base, in_cap - base), Ro};
+            GlobalMem m{mk_rsrc_clamped(in + base, in_cap - base), Ro};
             st = lz4_block(m, s0, end, N);
         }
         if (lane == 0) status[b] = (uint8_t)st;
@@ -464,9 +452,9 @@ __global__ __launch_bounds__(WAVE) void lz4_comp_kernel(const uint8_t *__restric
         const uint32_t len = (uint32_t)(in_offs[b + 1] - c0);
         const uint32_t s0 = (uint32_t)(c0 & 3);
         const uint64_t base = c0 - s0;
-        const Src F{mkr(in + base, in_cap - base), s0};
+        const Src F{mk_rsrc_clamped(in + base, in_cap - base), s0};
         Out O;
-        O.R = mkr(slots + slot_offs[b], slot_offs[b + 1] - slot_offs[b]);
+        O.R = mk_rsrc_clamped(slots + slot_offs[b], slot_offs[b + 1] - slot_offs[b]);
         O.op = 0;
         O.mis = (uint32_t)((uintptr_t)(slots + slot_offs[b]) & 3u);
         {   // varint32 length
@@ -502,7 +490,7 @@ __global__ __launch_bounds__(WAVE) void lz4_comp_kernel(const uint8_t *__restric
                 // (a repeat from far back, which later positions have pushed out of tab), read
                 // only where the entry's 16 hash bits agree
                 const uint32_t hv = x * 2654435761u, hf = hv >> (32 - FLOG), tag = (hv >> (16 - FLOG)) & 0xFFFFu;
-                if (ip == cb) h0 = rdl(hf, 0);
+                if (ip == cb) h0 = rl32(hf, 0);
                 const uint32_t c1 = cb + (valid ? (uint32_t)tab[h] : 0u);   // (an empty entry reads as the chunk's first position)
                 const uint32_t e = valid ? first[hf] : 0u, c2 = cb + (e >> 16);
                 const bool hit1 = valid && c1 < P && F.ld32(c1) == x;
@@ -518,7 +506,7 @@ __global__ __launch_bounds__(WAVE) void lz4_comp_kernel(const uint8_t *__restric
                     ip += WAVE;
                     continue;
                 }
-                const uint32_t ms = ip + sl, mc = rdl(c, sl);
+                const uint32_t ms = ip + sl, mc = rl32(c, sl);
                 const uint32_t ml = MINMATCH + match_len(F, mc + MINMATCH, ms + MINMATCH, mlim);
                 O.sequence(F, anchor, ms - anchor, ms - mc, ml);
                 ip = ms + ml;

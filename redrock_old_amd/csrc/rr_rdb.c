@@ -16,30 +16,6 @@
 
 #define fail rr_fail
 
-/* read / write exactly len bytes on a blocking fd: 1 done, 0 closed, -1 error
- * (the reference's _read_pipe_by_length / _write_pipe_by_length, rock_rdb.c:64-103) */
-static int read_full(int fd, void *buf, size_t len) {
-    char *p = (char *)buf;
-    while (len) {
-        ssize_t r = read(fd, p, len);
-        if (r == 0) return 0;
-        if (r < 0) { if (errno == EINTR) continue; return -1; }
-        p += r;
-        len -= (size_t)r;
-    }
-    return 1;
-}
-static int write_full(int fd, const void *buf, size_t len) {
-    const char *p = (const char *)buf;
-    while (len) {
-        ssize_t r = write(fd, p, len);
-        if (r < 0) { if (errno == EINTR) continue; return -1; }
-        p += r;
-        len -= (size_t)r;
-    }
-    return 1;
-}
-
 static uint8_t *pack_requests(const int *dbis, const char *const *keys, const size_t *key_lens, size_t k,
                               size_t *out_len, int tag) {
     size_t len = tag ? sizeof(int) + sizeof(size_t) : 0;
@@ -164,11 +140,11 @@ int rr_rdb_request_flat(int fd_req, int fd_resp, const int *dbis, const char *co
     size_t wlen = 0;
     uint8_t *req = pack_requests(dbis, keys, key_lens, k, &wlen, 1);
     if (!req) return fail(RR_API_ENOMEM, "malloc");
-    const int w = write_full(fd_req, req, wlen);   /* the service reads a whole FLAT request before it answers */
+    const int w = rr_write_full(fd_req, req, wlen);   /* the service reads a whole FLAT request before it answers */
     free(req);
     if (w != 1) return fail(RR_API_EINVAL, "request pipe write failed");
     uint64_t h[3];
-    if (read_full(fd_resp, h, sizeof h) != 1) return fail(RR_API_EINVAL, "pipe closed (flat header)");
+    if (rr_read_full(fd_resp, h, sizeof h) != 1) return fail(RR_API_EINVAL, "pipe closed (flat header)");
     out->n = h[0];
     out->n_elems = h[1];
     out->bytes = h[2];
@@ -176,8 +152,8 @@ int rr_rdb_request_flat(int fd_req, int fd_resp, const int *dbis, const char *co
     out->elems = (rr_elem *)malloc((h[1] ? h[1] : 1) * sizeof(rr_elem));
     out->arena = (uint8_t *)malloc(h[2] + 16);
     if (!out->values || !out->elems || !out->arena) { rr_rdb_flat_free(out); return fail(RR_API_ENOMEM, "malloc"); }
-    if (read_full(fd_resp, out->values, h[0] * sizeof(rr_value)) != 1 ||
-        read_full(fd_resp, out->elems, h[1] * sizeof(rr_elem)) != 1 || read_full(fd_resp, out->arena, h[2]) != 1) {
+    if (rr_read_full(fd_resp, out->values, h[0] * sizeof(rr_value)) != 1 ||
+        rr_read_full(fd_resp, out->elems, h[1] * sizeof(rr_elem)) != 1 || rr_read_full(fd_resp, out->arena, h[2]) != 1) {
         rr_rdb_flat_free(out);
         return fail(RR_API_EINVAL, "pipe closed (flat body)");
     }
@@ -227,10 +203,10 @@ static int reqs_push(reqs_t *r, int dbi, char *key, size_t len) {
 /* the rest of a request whose dbi was read: size_t key_len, key */
 static int read_key(int fd, int dbi, reqs_t *r) {
     size_t len;
-    if (read_full(fd, &len, sizeof len) != 1) return -1;
+    if (rr_read_full(fd, &len, sizeof len) != 1) return -1;
     char *key = (char *)malloc(len ? len : 1);
     if (!key) return -1;
-    if (len && read_full(fd, key, len) != 1) { free(key); return -1; }
+    if (len && rr_read_full(fd, key, len) != 1) { free(key); return -1; }
     if (reqs_push(r, dbi, key, len)) { free(key); return -1; }
     return 0;
 }
@@ -260,8 +236,8 @@ static int answer_save(int fd_resp, rr_ctx *ctx, const rr_value *vals, const rr_
     if (out && ts && offs &&
         rr_rdbsave_batch_host(ctx, vals, els, n_elems, arena, bytes, n, NULL, out, cap, offs, ts, ts + n, &t) == RR_API_OK) {
         const uint64_t h[2] = {n, offs[n]};
-        rc = (write_full(fd_resp, h, sizeof h) == 1 && write_full(fd_resp, ts, 2 * n) == 1 &&
-              write_full(fd_resp, offs, (n + 1) * sizeof(uint64_t)) == 1 && write_full(fd_resp, out, offs[n]) == 1)
+        rc = (rr_write_full(fd_resp, h, sizeof h) == 1 && rr_write_full(fd_resp, ts, 2 * n) == 1 &&
+              rr_write_full(fd_resp, offs, (n + 1) * sizeof(uint64_t)) == 1 && rr_write_full(fd_resp, out, offs[n]) == 1)
                  ? 0 : -1;
     }
     free(out); free(ts); free(offs);
@@ -271,10 +247,10 @@ static int answer_save(int fd_resp, rr_ctx *ctx, const rr_value *vals, const rr_
 static int serve_flat(int fd_req, int fd_resp, reqs_t *r, rr_rdb_multiget_fn get, void (*free_val)(void *), void *user,
                       rr_ctx *ctx, int save) {
     size_t k;
-    if (read_full(fd_req, &k, sizeof k) != 1) return -1;
+    if (rr_read_full(fd_req, &k, sizeof k) != 1) return -1;
     for (size_t i = 0; i < k; i++) {
         int dbi;
-        if (read_full(fd_req, &dbi, sizeof dbi) != 1 || read_key(fd_req, dbi, r)) return -1;
+        if (rr_read_full(fd_req, &dbi, sizeof dbi) != 1 || read_key(fd_req, dbi, r)) return -1;
     }
     if (!ctx || lookup(r, get, user)) { drop_vals(r, free_val); return -1; }
     uint64_t *offs = (uint64_t *)malloc((r->n + 1) * sizeof(uint64_t));
@@ -295,8 +271,8 @@ static int serve_flat(int fd_req, int fd_resp, reqs_t *r, rr_rdb_multiget_fn get
             rc = answer_save(fd_resp, ctx, vals, els, t.n_elems < cap ? t.n_elems : cap, arena, bytes, r->n);
         } else if (dec == RR_API_OK) {
             const uint64_t h[3] = {r->n, t.n_elems < cap ? t.n_elems : cap, bytes};
-            rc = (write_full(fd_resp, h, sizeof h) == 1 && write_full(fd_resp, vals, h[0] * sizeof(rr_value)) == 1 &&
-                  write_full(fd_resp, els, h[1] * sizeof(rr_elem)) == 1 && write_full(fd_resp, arena, bytes) == 1)
+            rc = (rr_write_full(fd_resp, h, sizeof h) == 1 && rr_write_full(fd_resp, vals, h[0] * sizeof(rr_value)) == 1 &&
+                  rr_write_full(fd_resp, els, h[1] * sizeof(rr_elem)) == 1 && rr_write_full(fd_resp, arena, bytes) == 1)
                      ? 0 : -1;
         }
     }
@@ -315,7 +291,7 @@ int rr_rdb_serve(int fd_req, int fd_resp, rr_rdb_multiget_fn get, void (*free_va
         int dbi;
         if (have_next) { dbi = next; have_next = 0; }
         else {
-            const int g = read_full(fd_req, &dbi, sizeof dbi);
+            const int g = rr_read_full(fd_req, &dbi, sizeof dbi);
             if (g == 0) break;                              /* normal exit: the child closed the pipe */
             if (g < 0) { rc = fail(RR_API_EINVAL, "request read error"); break; }
         }
@@ -333,14 +309,14 @@ int rr_rdb_serve(int fd_req, int fd_resp, rr_rdb_multiget_fn get, void (*free_va
             struct pollfd pf = {fd_req, POLLIN, 0};
             if (poll(&pf, 1, 0) <= 0 || !(pf.revents & POLLIN)) break;
             int d2;
-            const int g = read_full(fd_req, &d2, sizeof d2);
+            const int g = rr_read_full(fd_req, &d2, sizeof d2);
             if (g != 1) break;   /* (a close is seen again at the top of the loop) */
             if (d2 == RR_RDB_FLAT_TAG || d2 == RR_RDB_SAVE_TAG) { have_next = 1; next = d2; break; }
             if (read_key(fd_req, d2, &r)) { rc = -1; break; }
         }
         if (rc || lookup(&r, get, user)) { drop_vals(&r, free_val); rc = fail(RR_API_EINVAL, "lookup failed (missing key)"); break; }
         for (size_t i = 0; i < r.n && !rc; i++) {
-            if (write_full(fd_resp, &r.vlens[i], sizeof(size_t)) != 1 || write_full(fd_resp, r.vals[i], r.vlens[i]) != 1)
+            if (rr_write_full(fd_resp, &r.vlens[i], sizeof(size_t)) != 1 || rr_write_full(fd_resp, r.vals[i], r.vlens[i]) != 1)
                 rc = fail(RR_API_EINVAL, "response write error");
         }
         drop_vals(&r, free_val);

@@ -25,7 +25,7 @@
 // CRC kernels over the assembled bytes.  A section that does not fit out_cap is not written at all.
 #include <hip/hip_runtime.h>
 
-#include "rr_device.h"
+#include "rr_rdb_device.h"
 #include "rr_kernels.h"
 #include "../../include/rr_rdbfile.h"
 
@@ -43,9 +43,6 @@ constexpr uint64_t MAX_SLICE = 0x7FFFFFF0ull;
 constexpr uint64_t POLY = 0x95ac9329ac4bc9b5ull;  // 0xad93d23594c935a9 reflected
 constexpr uint64_t ONE = 1ull << 63;              // x^0 in the reflected bit order
 static_assert(PIECE == RR_WAVE * RUN && MAX_WAVES % RR_WAVE == 0 && RUN % 8 == 0, "a lane a run");
-
-struct __attribute__((packed, aligned(1))) u128_ua { uint32_t a, b, c, d; };
-typedef __attribute__((address_space(3))) uint64_t lds_u64;
 
 // ---- GF(2)[x] mod P, reflected: bit 63 - i is the coefficient of x^i --------------------------
 __host__ __device__ constexpr uint64_t gf_mulx(uint64_t a) { return (a >> 1) ^ (POLY & (0ull - (a & 1))); }
@@ -87,10 +84,6 @@ __device__ const LaneK RUN_K = make_run_k();
 __device__ const LaneK PART_K = make_part_k();
 constexpr uint64_t X_PIECE = gf_xpow8(PIECE);
 
-__device__ __forceinline__ uint32_t rfl(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint64_t first64(uint64_t x) { return (uint64_t)rfl((uint32_t)x) | ((uint64_t)rfl((uint32_t)(x >> 32)) << 32); }
-__device__ __forceinline__ uint32_t rl32(uint32_t x, uint32_t k) { return (uint32_t)__builtin_amdgcn_readlane((int)x, (int)k); }
-__device__ __forceinline__ uint64_t rl64(uint64_t x, uint32_t k) { return (uint64_t)rl32((uint32_t)x, k) | ((uint64_t)rl32((uint32_t)(x >> 32), k) << 32); }
 __device__ __forceinline__ uint64_t wave_xor(uint64_t x) {
 #pragma unroll
     for (int d = RR_WAVE / 2; d > 0; d >>= 1) x ^= __shfl_xor(x, d, RR_WAVE);
@@ -239,59 +232,13 @@ struct Sec {
     uint32_t flags;
 };
 
-__device__ __forceinline__ uint32_t len_bytes(uint64_t len) { return len < 64 ? 1u : len < 16384 ? 2u : len <= 0xFFFFFFFFull ? 5u : 9u; }
-__device__ __forceinline__ void put_be(uint8_t *d, uint64_t v, uint32_t nb) {
-#pragma unroll
-    for (uint32_t k = 0; k < 8; ++k)
-        if (k < nb) d[k] = (uint8_t)(v >> (8 * (nb - 1 - k)));
-}
-__device__ __forceinline__ void put_le(uint8_t *d, uint64_t v, uint32_t nb) {
-#pragma unroll
-    for (uint32_t k = 0; k < 8; ++k)
-        if (k < nb) d[k] = (uint8_t)(v >> (8 * k));
-}
-__device__ __forceinline__ uint32_t put_len(uint8_t *d, uint64_t len) {   // rdbSaveLen, rdb.c:147-178
-    if (len < 64) { d[0] = (uint8_t)len; return 1; }
-    if (len < 16384) { d[0] = (uint8_t)(0x40 | (len >> 8)); d[1] = (uint8_t)len; return 2; }
-    if (len <= 0xFFFFFFFFull) { d[0] = 0x80; put_be(d + 1, len, 4); return 5; }
-    d[0] = 0x81;
-    put_be(d + 1, len, 8);
-    return 9;
-}
-__device__ __forceinline__ uint32_t rint_bytes(int64_t v) { return v >= -128 && v <= 127 ? 2u : v >= -32768 && v <= 32767 ? 3u : 5u; }
-// rdbSaveRawString's integer branch (rdb.c:416-422, rdbTryIntegerEncoding :307-321)
-__device__ __forceinline__ bool raw_is_int(const uint8_t *s, uint32_t len, int64_t &v) {
-    return len <= 11 && zip_try_int(s, len, v) && v >= -2147483648ll && v <= 2147483647ll;
-}
 __device__ __forceinline__ bool slice_ok(uint64_t o0, uint64_t o1, uint64_t cap) { return o0 <= o1 && o1 <= cap && o1 - o0 < MAX_SLICE; }
 
-// the whole wave copies len bytes (wave-uniform arguments): bytes up to dst's 16-byte boundary, then
-// 16 bytes a lane (unaligned loads inside [src, src + len), aligned stores), then the tail bytes
-__device__ __forceinline__ void wave_copy(uint8_t *dst, const uint8_t *__restrict__ src, uint32_t len) {
-    const uint32_t lane = lane_id();
-    uint32_t head = (uint32_t)(0 - (uintptr_t)dst) & 15;
-    if (head > len) head = len;
-    if (lane < head) dst[lane] = src[lane];
-    const uint32_t body = (len - head) & ~15u;
-    dst += head;
-    src += head;
-    for (uint64_t k = (uint64_t)lane * 16; k < body; k += RR_WAVE * 16) {
-        const u128_ua x = *reinterpret_cast<const u128_ua *>(src + k);
-        *reinterpret_cast<uint4 *>(dst + k) = make_uint4(x.a, x.b, x.c, x.d);
-    }
-    if (lane < len - head - body) dst[body + lane] = src[body + lane];
-}
 // a lane's body: by the lane itself when short, else by the whole wave, the lanes' bodies in turn
 __device__ __forceinline__ void copy_bodies(uint8_t *dst, const uint8_t *__restrict__ src, uint32_t len, bool mine) {
     if (mine && len <= SHORT_BODY)
         for (uint32_t k = 0; k < len; ++k) dst[k] = src[k];
-    uint64_t m = __ballot(mine && len > SHORT_BODY);
-    while (m) {
-        const uint32_t k = (uint32_t)__builtin_ctzll(m);
-        m &= m - 1;
-        wave_copy(reinterpret_cast<uint8_t *>(rl64((uint64_t)(uintptr_t)dst, k)),
-                  reinterpret_cast<const uint8_t *>(rl64((uint64_t)(uintptr_t)src, k)), rl32(len, k));
-    }
+    wave_copy_each(dst, src, len, mine && len > SHORT_BODY);
 }
 
 // y[0] = head_bytes, y[1 + i] = record i's size, y[n + 1] = 0 (the scan's total); rec_status; and

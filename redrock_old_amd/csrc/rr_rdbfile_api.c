@@ -224,14 +224,10 @@ int rr_crc64_device(rr_ctx *c, const uint8_t *data, uint64_t bytes, uint64_t *d_
 
 int rr_rdbdump_batch(rr_ctx *c, const rr_blob_batch *in, const uint8_t *types, const uint8_t *status, rr_blob_batch *out,
                      uint8_t *out_status, rr_rdbfile_result *d_result, void *stream) {
-    if (!c || !in || !out || !d_result) return fail(RR_API_EINVAL, "NULL argument");
-    if (out->n != in->n) return fail(RR_API_EINVAL, "out->n != in->n");
-    if (in->n >= RR_MAX_VALUES) return fail(RR_API_EINVAL, "batch too large (value indices are 32-bit)");
-    if (!in->offsets || !out->offsets) return fail(RR_API_EINVAL, "NULL offsets");
-    if (in->n && (!types || !status || !out_status)) return fail(RR_API_EINVAL, "NULL buffer");
-    if ((in->data_cap && !in->data) || (out->data_cap && !out->data)) return fail(RR_API_EINVAL, "NULL buffer");
+    int rc = rr_check_blob_io(c, in, out, d_result, types && status && out_status);
+    if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
-    int rc = rr_ensure_scratch(c, rr_rdbdump_scratch_words(in->n), (hipStream_t)stream);
+    rc = rr_ensure_scratch(c, rr_rdbdump_scratch_words(in->n), (hipStream_t)stream);
     if (rc) return rc;
     HIPCHK(rr_launch_rdbdump(in->data, in->data_cap, in->offsets, types, status, in->n, out->data, out->data_cap, out->offsets,
                              out_status, c->scratch, d_result, (hipStream_t)stream));
@@ -240,14 +236,10 @@ int rr_rdbdump_batch(rr_ctx *c, const rr_blob_batch *in, const uint8_t *types, c
 
 int rr_rdbdump_verify_batch(rr_ctx *c, const rr_blob_batch *in, rr_blob_batch *out, uint8_t *types, uint8_t *status,
                             rr_rdbfile_result *d_result, void *stream) {
-    if (!c || !in || !out || !d_result) return fail(RR_API_EINVAL, "NULL argument");
-    if (out->n != in->n) return fail(RR_API_EINVAL, "out->n != in->n");
-    if (in->n >= RR_MAX_VALUES) return fail(RR_API_EINVAL, "batch too large (value indices are 32-bit)");
-    if (!in->offsets || !out->offsets) return fail(RR_API_EINVAL, "NULL offsets");
-    if (in->n && (!types || !status)) return fail(RR_API_EINVAL, "NULL buffer");
-    if ((in->data_cap && !in->data) || (out->data_cap && !out->data)) return fail(RR_API_EINVAL, "NULL buffer");
+    int rc = rr_check_blob_io(c, in, out, d_result, types && status);
+    if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
-    int rc = rr_ensure_scratch(c, rr_rdbdump_scratch_words(in->n), (hipStream_t)stream);
+    rc = rr_ensure_scratch(c, rr_rdbdump_scratch_words(in->n), (hipStream_t)stream);
     if (rc) return rc;
     HIPCHK(rr_launch_rdbdump_verify(in->data, in->data_cap, in->offsets, in->n, out->data, out->data_cap, out->offsets, types,
                                     status, c->scratch, d_result, (hipStream_t)stream));
@@ -255,17 +247,6 @@ int rr_rdbdump_verify_batch(rr_ctx *c, const rr_blob_batch *in, rr_blob_batch *o
 }
 
 /* ---- host-pointer forms ---------------------------------------------------------------------------- */
-#define GROW(P, C, N) do { int r_ = rr_dgrow((void **)&(P), &(C), (N)); if (r_) return r_; } while (0)
-#define UP(D, S, B) do { if ((B) != 0) HIPCHK(hipMemcpyAsync((D), (S), (B), hipMemcpyHostToDevice, c->stream)); } while (0)
-#define DOWN(D, S, B) do { if ((B) != 0) HIPCHK(hipMemcpyAsync((D), (S), (B), hipMemcpyDeviceToHost, c->stream)); } while (0)
-
-/* the bytes the slices reach; a slice past them does not exist on the device */
-static uint64_t reach(const uint64_t *offs, uint64_t n, uint64_t cap) {
-    uint64_t m = 0;
-    for (uint64_t i = 0; i <= n; i++)
-        if (offs[i] > m && offs[i] <= cap) m = offs[i];
-    return m;
-}
 static uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
 
 int rr_rdbfile_section_host(rr_ctx *c, const rr_rdbfile_in *in, uint32_t flags, uint8_t *out, uint64_t out_cap,
@@ -277,7 +258,7 @@ int rr_rdbfile_section_host(rr_ctx *c, const rr_rdbfile_in *in, uint32_t flags, 
     if (n && (((flags & RR_RDBFILE_IDLE) && !in->idle) || ((flags & RR_RDBFILE_FREQ) && !in->freq)))
         return fail(RR_API_EINVAL, "RR_RDBFILE_IDLE / RR_RDBFILE_FREQ without the array");
     if ((in->head_bytes && !in->head) || (out_cap && !out)) return fail(RR_API_EINVAL, "NULL buffer");
-    const uint64_t pb = reach(in->payloads.offsets, n, in->payloads.data_cap), kb = reach(in->keys.offsets, n, in->keys.data_cap);
+    const uint64_t pb = rr_reach(in->payloads.offsets, n, in->payloads.data_cap), kb = rr_reach(in->keys.offsets, n, in->keys.data_cap);
     if ((pb && !in->payloads.data) || (kb && !in->keys.data)) return fail(RR_API_EINVAL, "NULL buffer");
     HIPCHK(hipSetDevice(c->device));
     /* d_vals: expires | idle | state[2] | result | types | status | freq | rec_status | head */
@@ -326,7 +307,7 @@ int rr_rdbdump_batch_host(rr_ctx *c, const uint8_t *data, const uint64_t *offset
                           rr_rdbfile_result *result) {
     if (!c || !offsets || !out_offsets || (n && (!types || !status || !out_status)) || (out_cap && !out))
         return fail(RR_API_EINVAL, "NULL argument");
-    const uint64_t nb = reach(offsets, n, ~0ull);
+    const uint64_t nb = rr_reach(offsets, n, ~0ull);
     if (nb && !data) return fail(RR_API_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(c->device));
     GROW(c->d_in, c->c_in, nb + 16);
@@ -347,10 +328,8 @@ int rr_rdbdump_batch_host(rr_ctx *c, const uint8_t *data, const uint64_t *offset
     DOWN(&r, v, sizeof r);
     DOWN(out_offsets, c->d_ooff, (n + 1) * sizeof(uint64_t));
     DOWN(out_status, v + 32 + 2 * n, n);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (r.bytes == ~0ull) return fail(RR_API_EDEVICE, "rdbdump: device-side failure (look-back timeout)");
-    DOWN(out, c->d_out, r.bytes < out_cap ? r.bytes : out_cap);
-    HIPCHK(hipStreamSynchronize(c->stream));
+    rc = rr_host_finish(c, "rdbdump", &r.bytes, out, c->d_out, out_cap);
+    if (rc) return rc;
     if (result) *result = r;
     return RR_API_OK;
 }
@@ -360,7 +339,7 @@ int rr_rdbdump_verify_batch_host(rr_ctx *c, const uint8_t *data, const uint64_t 
                                  rr_rdbfile_result *result) {
     if (!c || !offsets || !out_offsets || (n && (!types || !status)) || (out_cap && !out))
         return fail(RR_API_EINVAL, "NULL argument");
-    const uint64_t nb = reach(offsets, n, ~0ull);
+    const uint64_t nb = rr_reach(offsets, n, ~0ull);
     if (nb && !data) return fail(RR_API_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(c->device));
     GROW(c->d_in, c->c_in, nb + 16);
@@ -380,10 +359,8 @@ int rr_rdbdump_verify_batch_host(rr_ctx *c, const uint8_t *data, const uint64_t 
     DOWN(out_offsets, c->d_ooff, (n + 1) * sizeof(uint64_t));
     DOWN(types, v + 32, n);
     DOWN(status, v + 32 + n, n);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (r.bytes == ~0ull) return fail(RR_API_EDEVICE, "rdbdump verify: device-side failure (look-back timeout)");
-    DOWN(out, c->d_out, r.bytes < out_cap ? r.bytes : out_cap);
-    HIPCHK(hipStreamSynchronize(c->stream));
+    rc = rr_host_finish(c, "rdbdump verify", &r.bytes, out, c->d_out, out_cap);
+    if (rc) return rc;
     if (result) *result = r;
     return RR_API_OK;
 }

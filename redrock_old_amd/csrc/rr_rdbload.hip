@@ -20,7 +20,7 @@
 // that is only copied is decompressed by the emit pass straight into its place in the blob.
 #include <hip/hip_runtime.h>
 
-#include "rr_device.h"
+#include "rr_rdb_device.h"
 #include "rr_kernels.h"
 #include "../../include/rr_rdbload.h"
 
@@ -34,22 +34,9 @@ constexpr uint32_t WIN = RR_RDBLOAD_LZF_NODE_MAX;   // a wave's LDS window, byte
 constexpr uint32_t MAX_SLICE = 0x7FFFFFF0u;         // a buffer resource's reach
 static_assert(WPB * WIN <= 65536 && WIN >= 64, "the windows are static LDS");
 
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
-struct __attribute__((packed, aligned(1))) u128_ua { uint32_t a, b, c, d; };
-
 struct Opt {
     uint32_t lru, set_ie, hash_e, hash_v, zset_e, zset_v;
 };
-
-__device__ __forceinline__ uint32_t rl32(uint32_t x, uint32_t k) { return (uint32_t)__builtin_amdgcn_readlane((int)x, (int)k); }
-__device__ __forceinline__ uint32_t rfl(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint64_t first64(uint64_t x) { return (uint64_t)rfl((uint32_t)x) | ((uint64_t)rfl((uint32_t)(x >> 32)) << 32); }
-__device__ __forceinline__ rsrc_t mk_rsrc(const void *base, uint32_t bytes) {   // wave-uniform arguments
-    return __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ uint32_t ld8(rsrc_t R, uint32_t k) { return __builtin_amdgcn_raw_buffer_load_b8(R, (int)k, 0, 0); }
-__device__ __forceinline__ void wait_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // little- and big-endian numbers out of a peeked register: byte i of the number is lane at + i
 __device__ __forceinline__ uint64_t le_lanes(uint32_t v, uint32_t at, uint32_t nb) {
@@ -62,29 +49,6 @@ __device__ __forceinline__ uint64_t be_lanes(uint32_t v, uint32_t at, uint32_t n
     for (uint32_t k = 0; k < nb; ++k) x = (x << 8) | rl32(v, at + k);
     return x;
 }
-__device__ __forceinline__ void put_le(uint8_t *d, uint64_t v, uint32_t nb) {   // one lane
-#pragma unroll
-    for (uint32_t k = 0; k < 8; ++k)
-        if (k < nb) d[k] = (uint8_t)(v >> (8 * k));
-}
-
-// the whole wave copies len bytes (wave-uniform arguments): bytes up to dst's 16-byte boundary, then
-// 16 bytes a lane (unaligned loads inside [src, src + len), aligned stores), then the tail bytes
-__device__ __forceinline__ void wave_copy(uint8_t *dst, const uint8_t *__restrict__ src, uint32_t len) {
-    const uint32_t lane = lane_id();
-    uint32_t head = (uint32_t)(0 - (uintptr_t)dst) & 15;
-    if (head > len) head = len;
-    if (lane < head) dst[lane] = src[lane];
-    const uint32_t body = (len - head) & ~15u;
-    dst += head;
-    src += head;
-    for (uint64_t k = (uint64_t)lane * 16; k < body; k += RR_WAVE * 16) {
-        const u128_ua x = *reinterpret_cast<const u128_ua *>(src + k);
-        *reinterpret_cast<uint4 *>(dst + k) = make_uint4(x.a, x.b, x.c, x.d);
-    }
-    if (lane < len - head - body) dst[body + lane] = src[body + lane];
-}
-
 // ---- the value's slice -------------------------------------------------------------------------
 struct Rd {
     rsrc_t R;               // exactly the slice
@@ -111,8 +75,6 @@ __device__ __forceinline__ uint32_t src_peek(const Rd &r, const Src &s, uint32_t
     if (s.lds) return k + lane < WIN ? (uint32_t)win[k + lane] : 0u;
     return ld8(r.R, s.off + k + lane);
 }
-
-__device__ __forceinline__ uint32_t dec_len_u(int64_t v) { return dec_len(v); }
 
 // rdbLoadLen (rdb.c:190-234) out of a peeked register, the length's first byte in lane i, avail
 // bytes left in the slice from there.  isenc: the 0xC0 form (val its low 6 bits).
@@ -288,7 +250,7 @@ __device__ __forceinline__ uint32_t rd_string(Rd &r, Str &s) {
         const uint64_t x = le_lanes(v, 1, w);
         s.kind = S_INT;
         s.iv = w == 1 ? (int64_t)(int8_t)x : w == 2 ? (int64_t)(int16_t)x : (int64_t)(int32_t)x;
-        s.len = dec_len_u(s.iv);
+        s.len = dec_len(s.iv);
         r.p += 1 + w;
         return RR_OK;
     }
@@ -450,7 +412,7 @@ __device__ __forceinline__ bool walk_node(const Rd &r, const Src &c, uint64_t L,
             if (isz == 0) iv = (int64_t)(enc & 0x0F) - 1;
             else if (isz == 8) iv = (int64_t)x;
             else iv = (int64_t)(x << (64 - 8 * isz)) >> (64 - 8 * isz);   // sign-extend isz bytes
-            const uint32_t dl = dec_len_u(iv);
+            const uint32_t dl = dec_len(iv);
             if (EMIT) {
                 if (lane == 0) {
                     put_le(out + pos, dl, 4);

@@ -35,12 +35,8 @@ int rr_rdbload_batch(rr_ctx *c, const rr_blob_batch *in, const uint8_t *types, r
     uint32_t k[6];
     int rc = resolve_opts(opts, k);   /* first: the options are checked whatever else is wrong */
     if (rc) return rc;
-    if (!c || !in || !out || !d_totals) return fail(RR_API_EINVAL, "NULL argument");
-    if (out->n != in->n) return fail(RR_API_EINVAL, "out->n != in->n");
-    if (in->n >= RR_MAX_VALUES) return fail(RR_API_EINVAL, "batch too large (value indices are 32-bit)");
-    if (!in->offsets || !out->offsets) return fail(RR_API_EINVAL, "NULL offsets");
-    if (in->n && (!types || !status)) return fail(RR_API_EINVAL, "NULL buffer");
-    if ((in->data_cap && !in->data) || (out->data_cap && !out->data)) return fail(RR_API_EINVAL, "NULL buffer");
+    rc = rr_check_blob_io(c, in, out, d_totals, types && status);
+    if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
     rc = rr_ensure_scratch(c, rr_rdbload_scratch_words(in->n), (hipStream_t)stream);
     if (rc) return rc;
@@ -48,8 +44,6 @@ int rr_rdbload_batch(rr_ctx *c, const rr_blob_batch *in, const uint8_t *types, r
                              status, c->scratch, d_totals, (hipStream_t)stream));
     return rr_mark_scratch(c, (hipStream_t)stream);
 }
-
-#define GROW(P, C, N) do { int r_ = rr_dgrow((void **)&(P), &(C), (N)); if (r_) return r_; } while (0)
 
 int rr_rdbload_batch_host(rr_ctx *c, const uint8_t *data, const uint64_t *offsets, const uint8_t *types, uint64_t n,
                           const rr_rdbload_opts *opts, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
@@ -59,9 +53,7 @@ int rr_rdbload_batch_host(rr_ctx *c, const uint8_t *data, const uint64_t *offset
     if (rc) return rc;
     if (!c || !offsets || !out_offsets || (n && (!types || !status)) || (out_cap && !out))
         return fail(RR_API_EINVAL, "NULL argument");
-    uint64_t nbytes = 0;   /* the bytes the slices reach; a slice past it does not exist on the device */
-    for (uint64_t i = 0; i <= n; i++)
-        if (offsets[i] > nbytes) nbytes = offsets[i];
+    const uint64_t nbytes = rr_reach(offsets, n, ~0ull);
     if (nbytes && !data) return fail(RR_API_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(c->device));
     GROW(c->d_in, c->c_in, nbytes + 16);
@@ -70,22 +62,19 @@ int rr_rdbload_batch_host(rr_ctx *c, const uint8_t *data, const uint64_t *offset
     GROW(c->d_out, c->c_out, out_cap + 16);
     GROW(c->d_ooff, c->c_ooff, (n + 1) * sizeof(uint64_t));
     uint8_t *d_types = (uint8_t *)c->d_vals, *d_status = d_types + n;
-    if (nbytes) HIPCHK(hipMemcpyAsync(c->d_in, data, nbytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    if (n) HIPCHK(hipMemcpyAsync(d_types, types, n, hipMemcpyHostToDevice, c->stream));
+    UP(c->d_in, data, nbytes);
+    UP(c->d_off, offsets, (n + 1) * sizeof(uint64_t));
+    UP(d_types, types, n);
     rr_blob_batch in = {(uint8_t *)c->d_in, (uint64_t *)c->d_off, n, nbytes};
     rr_blob_batch ob = {(uint8_t *)c->d_out, (uint64_t *)c->d_ooff, n, out_cap};
     rc = rr_rdbload_batch(c, &in, d_types, &ob, d_status, c->d_totals, opts, c->stream);
     if (rc) return rc;
     rr_totals t;
-    HIPCHK(hipMemcpyAsync(&t, c->d_totals, sizeof t, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(out_offsets, c->d_ooff, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (n) HIPCHK(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (t.bytes == ~0ull) return fail(RR_API_EDEVICE, "rdbload: device-side failure (look-back timeout)");
-    const uint64_t nb = t.bytes < out_cap ? t.bytes : out_cap;
-    if (nb) HIPCHK(hipMemcpyAsync(out, c->d_out, nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    DOWN(&t, c->d_totals, sizeof t);
+    DOWN(out_offsets, c->d_ooff, (n + 1) * sizeof(uint64_t));
+    DOWN(status, d_status, n);
+    rc = rr_host_finish(c, "rdbload", &t.bytes, out, c->d_out, out_cap);
+    if (rc) return rc;
     if (totals) *totals = t;
     return RR_API_OK;
 }

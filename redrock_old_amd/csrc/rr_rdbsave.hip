@@ -18,7 +18,7 @@
 // back when it opens the node, writes the prefix and places the entries behind it.
 #include <hip/hip_runtime.h>
 
-#include "rr_device.h"
+#include "rr_rdb_device.h"
 #include "rr_kernels.h"
 
 using namespace rr;
@@ -30,9 +30,6 @@ constexpr uint32_t GRID_CAP = 16384;    // workgroups: 65536 waves, 256 per CU o
 constexpr uint32_t LIST_GROUP = 8;      // values a wave of rdb_list_kernel looks at per step
 constexpr uint32_t SHORT_BODY = 32;     // a body of up to this many bytes is copied by its own lane
 
-typedef uint32_t u32_ua __attribute__((aligned(1)));
-struct __attribute__((packed, aligned(1))) u128_ua { uint32_t a, b, c, d; };
-
 struct ElemV {
     uint64_t data;
     uint32_t len, kind;
@@ -42,16 +39,6 @@ __device__ __forceinline__ ElemV get_elem(const rr_elem *e) {
     return {(uint64_t)x.x | ((uint64_t)x.y << 32), x.z, x.w & 0xFF};
 }
 __device__ __forceinline__ bool in_arena(const ElemV &e, uint64_t acap) { return e.data <= acap && e.len <= acap - e.data; }
-
-__device__ __forceinline__ uint64_t rl64(uint64_t x, uint32_t k) {   // k wave-uniform
-    return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, (int)k) |
-           ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), (int)k) << 32);
-}
-__device__ __forceinline__ uint32_t rl32(uint32_t x, uint32_t k) { return (uint32_t)__builtin_amdgcn_readlane((int)x, (int)k); }
-__device__ __forceinline__ uint64_t first64(uint64_t x) {
-    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x) |
-           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(x >> 32)) << 32);
-}
 
 // Wave64 inclusive scan of costs below 2^40 (a cost is at most 2^32 + 8), every lane active: the low
 // 24 bits and the rest scanned apart by the u32 DPP scan, which needs no per-step lane predicates
@@ -66,44 +53,6 @@ __device__ __forceinline__ uint64_t sum_lanes(uint64_t x) {
     const uint32_t a = wave_incl_scan_u32((uint32_t)x & 0xFFFFFFu), b = wave_incl_scan_u32((uint32_t)(x >> 24) & 0xFFFFFFu),
                    c = wave_incl_scan_u32((uint32_t)(x >> 48));
     return (uint64_t)rl32(a, RR_WAVE - 1) + ((uint64_t)rl32(b, RR_WAVE - 1) << 24) + ((uint64_t)rl32(c, RR_WAVE - 1) << 48);
-}
-
-// ---- rdbSaveLen (rdb.c:147-178) ----
-__device__ __forceinline__ uint32_t len_bytes(uint64_t len) {
-    return len < 64 ? 1u : len < 16384 ? 2u : len <= 0xFFFFFFFFull ? 5u : 9u;
-}
-// nb <= 8 bytes of v.  Unrolled into eight predicated stores: a loop over a lane's own byte count
-// is one more level of divergent control flow, and each level holds an exec mask in an SGPR pair.
-__device__ __forceinline__ void put_be(uint8_t *d, uint64_t v, uint32_t nb) {
-#pragma unroll
-    for (uint32_t k = 0; k < 8; ++k)
-        if (k < nb) d[k] = (uint8_t)(v >> (8 * (nb - 1 - k)));
-}
-__device__ __forceinline__ void put_le(uint8_t *d, uint64_t v, uint32_t nb) {
-#pragma unroll
-    for (uint32_t k = 0; k < 8; ++k)
-        if (k < nb) d[k] = (uint8_t)(v >> (8 * k));
-}
-__device__ __forceinline__ uint32_t put_len(uint8_t *d, uint64_t len) {
-    if (len < 64) { d[0] = (uint8_t)len; return 1; }
-    if (len < 16384) { d[0] = (uint8_t)(0x40 | (len >> 8)); d[1] = (uint8_t)len; return 2; }
-    if (len <= 0xFFFFFFFFull) { d[0] = 0x80; put_be(d + 1, len, 4); return 5; }
-    d[0] = 0x81;
-    put_be(d + 1, len, 8);
-    return 9;
-}
-// ---- rdbEncodeInteger (rdb.c:241-261) ----
-__device__ __forceinline__ bool is_i32(int64_t v) { return v >= -2147483648ll && v <= 2147483647ll; }
-__device__ __forceinline__ uint32_t rint_bytes(int64_t v) { return v >= -128 && v <= 127 ? 2u : v >= -32768 && v <= 32767 ? 3u : 5u; }
-__device__ __forceinline__ void put_rint(uint8_t *d, int64_t v) {
-    const uint32_t nb = rint_bytes(v) - 1;
-    d[0] = (uint8_t)(0xC0 | (nb == 1 ? 0 : nb == 2 ? 1 : 2));
-    put_le(d + 1, (uint64_t)v, nb);
-}
-// rdbSaveRawString's integer branch (rdb.c:416-422, rdbTryIntegerEncoding :307-321): up to 11 bytes
-// that are the canonical decimal (what ll2string gives back: string2ll's strict form) of an int32
-__device__ __forceinline__ bool raw_is_int(const uint8_t *s, uint32_t len, int64_t &v) {
-    return len <= 11 && zip_try_int(s, len, v) && is_i32(v);
 }
 
 // ---- ziplist entries (ziplist.c:332-364, :480-534) ----
@@ -124,34 +73,6 @@ __device__ __forceinline__ bool ql_allow(uint64_t node_sz, uint64_t est, uint32_
     const uint32_t new_sz = (uint32_t)(node_sz + est);   // unsigned int in the reference
     if (fill < 0) return new_sz <= (2048u << (uint32_t)(-fill));   // {4096 .. 65536}[-fill - 1]
     return new_sz <= 8192 && (int)count < fill;
-}
-
-// the whole wave copies len bytes (wave-uniform arguments): bytes up to dst's 16-byte boundary, then
-// 16 bytes a lane (unaligned loads inside [src, src + len), aligned stores), then the tail bytes
-__device__ __forceinline__ void wave_copy(uint8_t *dst, const uint8_t *__restrict__ src, uint32_t len) {
-    const uint32_t lane = lane_id();
-    uint32_t head = (uint32_t)(0 - (uintptr_t)dst) & 15;
-    if (head > len) head = len;
-    if (lane < head) dst[lane] = src[lane];
-    const uint32_t body = (len - head) & ~15u;
-    dst += head;   // 16-byte aligned from here
-    src += head;
-    for (uint64_t k = (uint64_t)lane * 16; k < body; k += RR_WAVE * 16) {
-        const u128_ua x = *reinterpret_cast<const u128_ua *>(src + k);
-        *reinterpret_cast<uint4 *>(dst + k) = make_uint4(x.a, x.b, x.c, x.d);
-    }
-    if (lane < len - head - body) dst[body + lane] = src[body + lane];
-}
-
-// a lane's long bodies, one after the other by the whole wave
-__device__ __forceinline__ void copy_long(uint8_t *dst, const uint8_t *__restrict__ src, uint32_t len, bool mine) {
-    uint64_t m = __ballot(mine);
-    while (m) {
-        const uint32_t k = (uint32_t)__builtin_ctzll(m);
-        m &= m - 1;
-        wave_copy(reinterpret_cast<uint8_t *>(rl64((uint64_t)(uintptr_t)dst, k)),
-                  reinterpret_cast<const uint8_t *>(rl64((uint64_t)(uintptr_t)src, k)), rl32(len, k));
-    }
 }
 
 // ---- LZF (rdbSaveLzfStringObject, rdb.c:348-364; the stream format of lzf_d.c:68-184) -------
@@ -182,15 +103,8 @@ constexpr uint32_t LZF_MIN_LEN = 21;           // rdb.c:426: len > 20
 constexpr uint32_t LZF_MAX_LEN = 0x7FFFFFF0u;  // a buffer resource's reach; longer strings stay raw
 constexpr uint32_t LZF_WINDOW = 8192, LZF_MAX_MATCH = 264, LZF_RUN = 32, LZF_CHUNK = 1u << 16;
 
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-
-__device__ __forceinline__ rsrc_t mk_rsrc(const void *base, uint32_t bytes) {   // wave-uniform arguments
-    return __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ uint32_t lzf_ld8(rsrc_t R, uint32_t k) { return __builtin_amdgcn_raw_buffer_load_b8(R, (int)k, 0, 0); }
 __device__ __forceinline__ uint32_t lzf_ld24(rsrc_t R, uint32_t k) {
-    return lzf_ld8(R, k) | (lzf_ld8(R, k + 1) << 8) | (lzf_ld8(R, k + 2) << 16);
+    return ld8(R, k) | (ld8(R, k + 1) << 8) | (ld8(R, k + 2) << 16);
 }
 __device__ __forceinline__ uint32_t lzf_hash(uint32_t x) { return (x * 2654435761u) >> (32 - LZF_HLOG); }
 
@@ -236,7 +150,7 @@ __device__ __forceinline__ uint32_t lzf_sequence(rsrc_t R, rsrc_t O, uint32_t op
                 const uint32_t run = lits - k < LZF_RUN ? lits - k : LZF_RUN;
                 __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(run - 1), O, (int)at, 0, 0);
             }
-            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)lzf_ld8(R, from + k), O, (int)(at + 1), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)ld8(R, from + k), O, (int)(at + 1), 0, 0);
         }
         const uint32_t o = off - 1;
         const uint32_t v = l < 7 ? ((l << 5) | (o >> 8)) | ((o & 0xFF) << 8)
@@ -292,7 +206,7 @@ __device__ __forceinline__ uint32_t lzf_compress(Lzf &Z, const uint8_t *src, uin
         uint32_t ml = 3;
         for (;;) {
             const uint32_t k = ml + lane;
-            const bool stop = k >= LZF_MAX_MATCH || ms + k >= len || lzf_ld8(R, mc + k) != lzf_ld8(R, ms + k);
+            const bool stop = k >= LZF_MAX_MATCH || ms + k >= len || ld8(R, mc + k) != ld8(R, ms + k);
             const uint64_t sb = __ballot(stop);
             if (sb) { ml += (uint32_t)__builtin_ctzll(sb); break; }
             ml += RR_WAVE;
@@ -451,7 +365,7 @@ __device__ uint64_t save_plain(const Batch &B, LzfCtx &X, uint32_t type, uint32_
                     for (uint32_t k = 0; k < e.len; ++k) dbody[k] = B.arena[e.data + k];
             }
         }
-        if (EMIT) copy_long(dbody, B.arena + e.data, e.len, active && form == 0 && e.len > SHORT_BODY);
+        if (EMIT) wave_copy_each(dbody, B.arena + e.data, e.len, active && form == 0 && e.len > SHORT_BODY);
         if (EMIT && LZF) {
             uint64_t m = __ballot(active && form == 4);
             while (m) {
@@ -576,7 +490,7 @@ __device__ uint64_t save_list(const Batch &B, uint32_t eb, uint32_t n, uint8_t *
                         for (uint32_t k = 0; k < e.len; ++k) d[k] = B.arena[e.data + k];
                 }
             }
-            copy_long(d, B.arena + e.data, e.len, active && !isint && e.len > SHORT_BODY);
+            wave_copy_each(d, B.arena + e.data, e.len, active && !isint && e.len > SHORT_BODY);
         }
     }
     if (open) close_node();

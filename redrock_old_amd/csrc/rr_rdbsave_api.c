@@ -3,10 +3,8 @@
  * §8f row f4): argument checks, the context's scratch, the host-pointer form that stages through
  * the context's device buffers, and the child side of the pipe mode (RR_RDB_SAVE_TAG, rr_rdb.h).
  */
-#include <errno.h>
 #include <stdlib.h>
 #include <string.h>
-#include <unistd.h>
 
 #include "rr_internal.h"
 #include "../../include/rr_rdb.h"
@@ -44,8 +42,6 @@ int rr_rdbsave_batch(rr_ctx *c, const rr_flat_batch *in, rr_blob_batch *out, uin
     return rr_mark_scratch(c, (hipStream_t)stream);
 }
 
-#define GROW(P, C, N) do { int r_ = rr_dgrow((void **)&(P), &(C), (N)); if (r_) return r_; } while (0)
-
 int rr_rdbsave_batch_host(rr_ctx *c, const rr_value *values, const rr_elem *elems, uint64_t n_elems,
                           const uint8_t *arena, uint64_t arena_bytes, uint64_t n, const rr_rdbsave_opts *opts,
                           uint8_t *data, uint64_t data_cap, uint64_t *offsets, uint8_t *types, uint8_t *status,
@@ -60,51 +56,26 @@ int rr_rdbsave_batch_host(rr_ctx *c, const rr_value *values, const rr_elem *elem
     GROW(c->d_out, c->c_out, data_cap + 16);
     GROW(c->d_ooff, c->c_ooff, (n + 1) * sizeof(uint64_t));
     GROW(c->d_in, c->c_in, 2 * n + 16);   /* types, status */
-    if (n) HIPCHK(hipMemcpyAsync(c->d_vals, values, n * sizeof(rr_value), hipMemcpyHostToDevice, c->stream));
-    if (n_elems) HIPCHK(hipMemcpyAsync(c->d_elems, elems, n_elems * sizeof(rr_elem), hipMemcpyHostToDevice, c->stream));
-    if (arena_bytes) HIPCHK(hipMemcpyAsync(c->d_arena, arena, arena_bytes, hipMemcpyHostToDevice, c->stream));
+    UP(c->d_vals, values, n * sizeof(rr_value));
+    UP(c->d_elems, elems, n_elems * sizeof(rr_elem));
+    UP(c->d_arena, arena, arena_bytes);
     rr_flat_batch in = {(rr_value *)c->d_vals, (rr_elem *)c->d_elems, (uint8_t *)c->d_arena, n, n_elems, arena_bytes};
     rr_blob_batch out = {(uint8_t *)c->d_out, (uint64_t *)c->d_ooff, n, data_cap};
     uint8_t *d_types = (uint8_t *)c->d_in, *d_status = d_types + n;
     int rc = rr_rdbsave_batch(c, &in, &out, d_types, d_status, c->d_totals, opts, c->stream);
     if (rc) return rc;
     rr_totals t;
-    HIPCHK(hipMemcpyAsync(&t, c->d_totals, sizeof t, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(offsets, c->d_ooff, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (n) HIPCHK(hipMemcpyAsync(types, d_types, n, hipMemcpyDeviceToHost, c->stream));
-    if (n) HIPCHK(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (t.bytes == ~0ull) return fail(RR_API_EDEVICE, "rdbsave: device-side failure (look-back timeout)");
-    const uint64_t nb = t.bytes < data_cap ? t.bytes : data_cap;
-    if (nb) HIPCHK(hipMemcpyAsync(data, c->d_out, nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    DOWN(&t, c->d_totals, sizeof t);
+    DOWN(offsets, c->d_ooff, (n + 1) * sizeof(uint64_t));
+    DOWN(types, d_types, n);
+    DOWN(status, d_status, n);
+    rc = rr_host_finish(c, "rdbsave", &t.bytes, data, c->d_out, data_cap);
+    if (rc) return rc;
     if (totals) *totals = t;
     return RR_API_OK;
 }
 
 /* ---- pipe mode, child side ------------------------------------------------------------------ */
-static int read_full(int fd, void *buf, size_t len) {
-    char *p = (char *)buf;
-    while (len) {
-        ssize_t r = read(fd, p, len);
-        if (r == 0) return 0;
-        if (r < 0) { if (errno == EINTR) continue; return -1; }
-        p += r;
-        len -= (size_t)r;
-    }
-    return 1;
-}
-static int write_full(int fd, const void *buf, size_t len) {
-    const char *p = (const char *)buf;
-    while (len) {
-        ssize_t r = write(fd, p, len);
-        if (r < 0) { if (errno == EINTR) continue; return -1; }
-        p += r;
-        len -= (size_t)r;
-    }
-    return 1;
-}
-
 void rr_rdbsave_result_free(rr_rdbsave_result *r) {
     if (!r) return;
     free(r->types);
@@ -130,11 +101,11 @@ int rr_rdbsave_request(int fd_req, int fd_resp, const int *dbis, const char *con
         memcpy(p, &key_lens[i], sizeof(size_t)); p += sizeof(size_t);
         memcpy(p, keys[i], key_lens[i]); p += key_lens[i];
     }
-    const int w = write_full(fd_req, req, len);   /* the service reads a whole request before it answers */
+    const int w = rr_write_full(fd_req, req, len);   /* the service reads a whole request before it answers */
     free(req);
     if (w != 1) return fail(RR_API_EINVAL, "request pipe write failed");
     uint64_t h[2];
-    if (read_full(fd_resp, h, sizeof h) != 1) return fail(RR_API_EINVAL, "pipe closed (save header)");
+    if (rr_read_full(fd_resp, h, sizeof h) != 1) return fail(RR_API_EINVAL, "pipe closed (save header)");
     out->n = h[0];
     out->bytes = h[1];
     out->types = (uint8_t *)malloc(h[0] ? h[0] : 1);
@@ -145,9 +116,9 @@ int rr_rdbsave_request(int fd_req, int fd_resp, const int *dbis, const char *con
         rr_rdbsave_result_free(out);
         return fail(RR_API_ENOMEM, "malloc");
     }
-    if ((h[0] && (read_full(fd_resp, out->types, h[0]) != 1 || read_full(fd_resp, out->status, h[0]) != 1)) ||
-        read_full(fd_resp, out->offsets, (h[0] + 1) * sizeof(uint64_t)) != 1 ||
-        (h[1] && read_full(fd_resp, out->data, h[1]) != 1)) {
+    if ((h[0] && (rr_read_full(fd_resp, out->types, h[0]) != 1 || rr_read_full(fd_resp, out->status, h[0]) != 1)) ||
+        rr_read_full(fd_resp, out->offsets, (h[0] + 1) * sizeof(uint64_t)) != 1 ||
+        (h[1] && rr_read_full(fd_resp, out->data, h[1]) != 1)) {
         rr_rdbsave_result_free(out);
         return fail(RR_API_EINVAL, "pipe closed (save body)");
     }

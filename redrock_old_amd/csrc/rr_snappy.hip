@@ -21,12 +21,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rr_device.h"
 #include "rr_kernels.h"
 #include "../../include/rr_snappy.h"
+
+using namespace rr;
 
 namespace {
 
 constexpr uint32_t WAVE = 64;
+static_assert(WAVE == RR_WAVE, "the shared wave helpers");
 constexpr uint32_t FRAG = 1u << 16;        // snappy kBlockSize (snappy.h:197-198)
 constexpr uint32_t TAB_MIN = 1u << 8;      // kMinHashTableSize
 constexpr uint32_t TAB_MAX = 1u << 14;     // kMaxHashTableSize
@@ -52,21 +56,7 @@ constexpr uint32_t SNZ_FRAG_LDS = RR_SNZ_FRAG;
 #define RR_SNZ_SPEC 1
 #endif
 
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-// LDS pointers kept in address space 3, so accesses compile to ds_* (a generic pointer gives flat_*
-// instructions, whose waits also drain every outstanding global store of the wave)
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
-typedef __attribute__((address_space(3))) uint16_t lds_u16;
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-__device__ __forceinline__ rsrc_t mkr(const void *base, uint64_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)(bytes < 0x7FFFFFF0ull ? bytes : 0x7FFFFFF0ull),
-                                             0x00020000);
-}
-__device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }
-__device__ __forceinline__ uint32_t rdl(uint32_t v, uint32_t l) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
-}
 
 // ---- decompression ------------------------------------------------------------------------
 #ifdef RR_PROBE
@@ -136,7 +126,7 @@ struct Win {
     __device__ __forceinline__ uint32_t dw(uint32_t q) const {
         const uint32_t r = q - wb, k = (r >> 2) & 3;
         const uint32_t v = k == 0 ? x[0] : k == 1 ? x[1] : k == 2 ? x[2] : x[3];
-        return rdl(v, r >> 4);
+        return rl32(v, r >> 4);
     }
     // 5+ bytes starting at q (uniform), low byte first
     __device__ __forceinline__ uint64_t bytes(uint32_t q) const {
@@ -145,8 +135,6 @@ struct Win {
         return v >> (8 * (q & 3));
     }
 };
-
-__device__ __forceinline__ void wait_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // wave64 inclusive scan (u32) in DPP: row shifts within each 16-lane row, then the rows' last
 // lanes carried up by row_bcast:15 / row_bcast:31 (as rr_device.h's wave_incl_scan_u32)
@@ -175,7 +163,7 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) {
     x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false));
     x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false));
     x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false));
-    return rdl(x, WAVE - 1);
+    return rl32(x, WAVE - 1);
 }
 
 // Byte copies inside the LDS window, a lane each (lanes with `mine`): l bytes from s to d, 16 a
@@ -334,7 +322,7 @@ __device__ uint32_t dec_block_lds(rsrc_t R, uint32_t s0, uint32_t clen, uint32_t
                 uint32_t v = sp[0];
 #pragma unroll
                 for (uint32_t k = 1; k < (PP + 1) / 2; ++k) v = (j >> 1) == k ? sp[k] : v;
-                const uint32_t pair = rdl(v, l);
+                const uint32_t pair = rl32(v, l);
                 const uint32_t sz = PP == 1 ? pair : (j & 1) ? pair >> 16 : pair & 0xFFFF;
                 tp = lane == nt ? p : tp;
                 ++nt;
@@ -442,7 +430,7 @@ __device__ uint32_t dec_block_lds(rsrc_t R, uint32_t s0, uint32_t clen, uint32_t
         const bool iscop = act && !lit;
         m = __ballot(iscop);
         if (m) {
-            const uint32_t c0 = rdl(tpos, (uint32_t)__builtin_ctzll(m));
+            const uint32_t c0 = rl32(tpos, (uint32_t)__builtin_ctzll(m));
             const bool indep = iscop && off >= len && tpos - off + len <= c0;
             lane_copies(win, indep, tpos - off, tpos, len);
             m = __ballot(iscop && !indep);
@@ -531,12 +519,12 @@ __global__ __launch_bounds__(WAVE) void snz_dec_kernel(const uint8_t *__restrict
         const uint32_t s0 = (uint32_t)(c0 & 3);
         const uint64_t base = c0 - s0;   // (whole dwords: the buffer's padding, not past it)
         uint8_t *gout = out + o0;
-        const rsrc_t Ro = mkr(gout, expected);
+        const rsrc_t Ro = mk_rsrc_clamped(gout, expected);
         uint32_t st = RR_SNAPPY_OK;
         bool bail = !(expected <= wcap && ((s0 + clen + 15) & ~15ull) <= wcap);
         if (!bail) {
             const uint64_t span = (s0 + clen + 15) & ~15ull;
-            st = dec_block_lds(mkr(in + base, span < in_cap - base ? span : in_cap - base), s0, (uint32_t)clen, expected,
+            st = dec_block_lds(mk_rsrc_clamped(in + base, span < in_cap - base ? span : in_cap - base), s0, (uint32_t)clen, expected,
                                win, wcap, bail);
             SNZP(const uint64_t po0 = snz_stamp();)
             if (!bail && st == RR_SNAPPY_OK) {   // LDS -> output: bytes to a 4-aligned address, 16 B per lane, bytes
@@ -561,7 +549,7 @@ __global__ __launch_bounds__(WAVE) void snz_dec_kernel(const uint8_t *__restrict
             }
             SNZP(if (lane == 0) atomicAdd(&g_snz_probe[5], (unsigned long long)(snz_stamp() - po0));)
         }
-        if (bail) st = dec_block_global(mkr(in + base, in_cap - base), s0, (uint32_t)clen, expected, Ro);
+        if (bail) st = dec_block_global(mk_rsrc_clamped(in + base, in_cap - base), s0, (uint32_t)clen, expected, Ro);
         if (lane == 0) status[b] = (uint8_t)st;
     }
 }
@@ -814,12 +802,12 @@ __device__ bool compress_fragment(const Frag &F, uint32_t fn, HTab<SPARSE> table
                     if (claimed(cl)) return false;
                     if (sl < K) {
                         if (!hit) goto remainder;
-                        ip = rdl(P, sl);
-                        cand = rdl(c, sl);
+                        ip = rl32(P, sl);
+                        cand = rl32(c, sl);
                         break;
                     }
-                    P0 = rdl(Pn, K - 1);
-                    S0 = rdl(S + B, K - 1);
+                    P0 = rl32(Pn, K - 1);
+                    S0 = rl32(S + B, K - 1);
                     K = K < RR_SNZ_K ? 2 * K : K;
                 }
             }
@@ -883,10 +871,10 @@ __global__ __launch_bounds__(WAVE) void snz_comp_kernel(const uint8_t *__restric
         const uint64_t c0 = in_offs[b], len = in_offs[b + 1] - c0;
         const uint32_t s0 = (uint32_t)(c0 & 3);
         Frag F;
-        F.R = mkr(in + (c0 - s0), in_cap - (c0 - s0));
+        F.R = mk_rsrc_clamped(in + (c0 - s0), in_cap - (c0 - s0));
         F.ib = ib;
         Out O;
-        O.R = mkr(slots + slot_offs[b], slot_offs[b + 1] - slot_offs[b]);
+        O.R = mk_rsrc_clamped(slots + slot_offs[b], slot_offs[b + 1] - slot_offs[b]);
         O.op = 0;
         O.mis = (uint32_t)((uintptr_t)(slots + slot_offs[b]) & 3u);
         {   // varint32 length
@@ -912,7 +900,7 @@ __global__ __launch_bounds__(WAVE) void snz_comp_kernel(const uint8_t *__restric
                            // every granule's load in flight at once, then the LDS stores
                 constexpr uint32_t SG = SNZ_FRAG_LDS ? (SNZ_FRAG_LDS + 15) / 16 / WAVE + 1 : 1;
                 const uint64_t ab = (c0 + f) & ~15ull;
-                const rsrc_t RS = mkr(in + ab, in_cap - ab);
+                const rsrc_t RS = mk_rsrc_clamped(in + ab, in_cap - ab);
                 const uint32_t ng = (F.sh + fn + 8 + 15) / 16;
                 u32x4_t v[SG];
 #pragma unroll

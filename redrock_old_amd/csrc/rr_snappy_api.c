@@ -52,7 +52,6 @@ int rr_snappy_decompress_batch(rr_ctx *c, const rr_blob_batch *in, rr_blob_batch
     return rr_mark_scratch(c, (hipStream_t)stream);
 }
 
-#define GROW(P, C, N) do { int r_ = rr_dgrow((void **)&(P), &(C), (N)); if (r_) return r_; } while (0)
 
 int rr_snappy_compress_batch_host(rr_ctx *c, const uint8_t *data, const uint64_t *offsets, uint64_t n, uint8_t *out,
                                   uint64_t out_cap, uint64_t *out_offsets) {
@@ -65,16 +64,16 @@ int rr_snappy_compress_batch_host(rr_ctx *c, const uint8_t *data, const uint64_t
     GROW(c->d_off, c->c_off, (n + 1) * sizeof(uint64_t));
     GROW(c->d_out, c->c_out, cap + 16);
     GROW(c->d_ooff, c->c_ooff, (n + 1) * sizeof(uint64_t));
-    if (bytes) HIPCHK(hipMemcpyAsync(c->d_in, data, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    UP(c->d_in, data, bytes);
+    UP(c->d_off, offsets, (n + 1) * sizeof(uint64_t));
     rr_blob_batch in = {(uint8_t *)c->d_in, (uint64_t *)c->d_off, n, pbytes};
     rr_blob_batch o = {(uint8_t *)c->d_out, (uint64_t *)c->d_ooff, n, cap};
     int rc = rr_snappy_compress_batch(c, &in, &o, c->stream);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out_offsets, c->d_ooff, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    DOWN(out_offsets, c->d_ooff, (n + 1) * sizeof(uint64_t));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (out_offsets[n] > out_cap) return fail(RR_API_EDEVICE, "compressed output larger than its bound");
-    if (out_offsets[n]) HIPCHK(hipMemcpyAsync(out, c->d_out, out_offsets[n], hipMemcpyDeviceToHost, c->stream));
+    DOWN(out, c->d_out, out_offsets[n]);
     HIPCHK(hipStreamSynchronize(c->stream));
     return RR_API_OK;
 }
@@ -89,18 +88,18 @@ int rr_snappy_decompress_batch_host(rr_ctx *c, const uint8_t *data, const uint64
     GROW(c->d_ooff, c->c_ooff, (n + 1) * sizeof(uint64_t));
     GROW(c->d_vals, c->c_vals, n + 16);   /* per-block status */
     GROW(c->d_out, c->c_out, out_cap + 16);
-    if (bytes) HIPCHK(hipMemcpyAsync(c->d_in, data, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_off, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    UP(c->d_in, data, bytes);
+    UP(c->d_off, offsets, (n + 1) * sizeof(uint64_t));
     rr_blob_batch in = {(uint8_t *)c->d_in, (uint64_t *)c->d_off, n, pbytes};
     rr_blob_batch o = {(uint8_t *)c->d_out, (uint64_t *)c->d_ooff, n, out_cap};
     int rc = rr_snappy_decompress_batch(c, &in, &o, (uint8_t *)c->d_vals, c->stream);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out_offsets, c->d_ooff, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (n) HIPCHK(hipMemcpyAsync(status, c->d_vals, n, hipMemcpyDeviceToHost, c->stream));
+    DOWN(out_offsets, c->d_ooff, (n + 1) * sizeof(uint64_t));
+    DOWN(status, c->d_vals, n);
     HIPCHK(hipStreamSynchronize(c->stream));
     if (out_offsets[n] > out_cap) return fail(RR_API_EINVAL, "out_cap %llu < announced output %llu",
                                               (unsigned long long)out_cap, (unsigned long long)out_offsets[n]);
-    if (out_offsets[n]) HIPCHK(hipMemcpyAsync(out, c->d_out, out_offsets[n], hipMemcpyDeviceToHost, c->stream));
+    DOWN(out, c->d_out, out_offsets[n]);
     HIPCHK(hipStreamSynchronize(c->stream));
     return RR_API_OK;
 }
