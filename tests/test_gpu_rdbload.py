@@ -1,7 +1,13 @@
 """rr_rdbload_batch on the GPU against tests/rdbload_reference.py: every status, offset, blob byte
 and total, with a canary behind every buffer the call writes.  The batches are the smallest that
 reach the kernels' paths: the header forms, the LZF sequences at their limits, the copy paths at
-every source alignment, the ziplist entry classes of a List node, one stride of the grid."""
+every source alignment, the ziplist entry classes of a List node, one stride of the grid.
+
+Corrupt input and the kernels' own seams are in tests/test_gpu_rdbload_edges.py (it imports
+run_device / compare / check from here): the mutation corpus of tests/rdbload_mutants.py (checked on
+the CPU by tests/test_rdbload_mutants.py) in two orders, truncated values with their missing bytes
+directly behind them, bad input offsets, LZF sequences and ziplist entries at every position round
+the 64-byte reloads, and the LDS window at its limits."""
 import struct
 
 import numpy as np
@@ -26,13 +32,16 @@ def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).cuda()
 
 
-def run_device(engine, types, data, offsets, opts, cap, room, stream=None):
+def run_device(engine, types, data, offsets, opts, cap, room, stream=None, d_data=None):
+    """d_data: the payload bytes already on the device (tests/test_gpu_rdbload_edges.py passes a slice
+    of a longer tensor, so that the call's data_cap is not the allocation's end)."""
     n = len(types)
     out = torch.full((room,), CANARY, dtype=torch.uint8, device="cuda")
     d_off = torch.full((n + 1 + 4,), 7, dtype=torch.int64, device="cuda")
     d_status = torch.full((n + 16,), CANARY, dtype=torch.uint8, device="cuda")
     d_tot = torch.full((4 + 2,), -3, dtype=torch.int64, device="cuda")
-    d_data = _dev(data) if len(data) else torch.zeros(0, dtype=torch.uint8, device="cuda")
+    if d_data is None:
+        d_data = _dev(data) if len(data) else torch.zeros(0, dtype=torch.uint8, device="cuda")
     d_in_off = torch.from_numpy(np.ascontiguousarray(offsets, np.uint64).view(np.int64).copy()).cuda()
     d_types = _dev(np.asarray(types, np.uint8)) if n else torch.zeros(0, dtype=torch.uint8, device="cuda")
     args = (d_data, d_in_off, d_types, out[:cap], d_off[:n + 1], d_status[:n], d_tot[:4])
