@@ -1,4 +1,5 @@
-/* rr_kernels.h — launch entry points of rr_kernels.hip, called by the C host layer (rr_api.c). */
+/* rr_kernels.h — launch entry points of rr_kernels.hip and rr_util.hip, called by the C host
+ * layer (rr_api.c). */
 #ifndef RR_KERNELS_H
 #define RR_KERNELS_H
 

@@ -1,6 +1,6 @@
-"""Every compile-time knob the kernel sources keep (rr_kernels.hip, rr_decode_class.h,
-rr_snappy.hip) still compiles for gfx950 with a non-default value, so no kept path rots: a
-front-end pass (templates instantiated, static_asserts checked) of each variant's device code.
+"""Every compile-time knob the kernel sources keep (rr_kernels.hip, rr_util.hip,
+rr_decode_class.h, rr_snappy.hip) still compiles for gfx950 with a non-default value, so no kept
+path rots: a front-end pass (templates instantiated, static_asserts checked) of each variant's device code.
 The default build is compiled in full by __graft_entry__.build().  CPU only (hipcc
 cross-compiles); skipped where hipcc is absent."""
 import os
@@ -22,6 +22,10 @@ VARIANTS = [
     ("rr_kernels.hip", "-DRR_ABLATE=4"),
     ("rr_kernels.hip", "-DRR_ABLATE=5"),
     ("rr_kernels.hip", "-DRR_ABLATE=6"),
+    ("rr_kernels.hip", "-DRR_ABLATE=7"),
+    ("rr_kernels.hip", "-DRR_ABLATE=8"),
+    ("rr_kernels.hip", "-DRR_ABLATE=9"),
+    ("rr_kernels.hip", "-DRR_ABLATE=10"),
     ("rr_kernels.hip", "-DRR_DEC_W=65536"),
     ("rr_kernels.hip", "-DRR_DEC_SLACK=8192"),
     ("rr_kernels.hip", "-DRR_DEC_NW=4"),
@@ -47,7 +51,7 @@ def _knobs(src):
 
 def test_every_knob_has_a_variant():
     """The variant list covers every RR_* knob the sources test (and they stay few)."""
-    knobs = _knobs("rr_kernels.hip") | _knobs("rr_decode_class.h") | _knobs("rr_snappy.hip")
+    knobs = _knobs("rr_kernels.hip") | _knobs("rr_util.hip") | _knobs("rr_decode_class.h") | _knobs("rr_snappy.hip")
     covered = set(re.findall(r"-D(RR_[A-Z0-9_]+)", " ".join(f for _, f in VARIANTS)))
     assert knobs <= covered, sorted(knobs - covered)
     assert len(knobs) <= 16, sorted(knobs)

@@ -1,22 +1,21 @@
 #!/bin/bash
-# Builds the kernels of a git revision as redrock_old_amd/librr_serdes_<name>.so (A/B timing
-# against the working tree on the same GPU box; diagnostics only).  The host objects are the
-# working tree's, so the launch ABI (rr_kernels.h) must be unchanged between the two.
+# Builds the engine library of a git revision as redrock_old_amd/librr_serdes_<name>.so (A/B timing
+# against the working tree on the same GPU box; diagnostics only): the revision's csrc/ and
+# include/ extracted under build/ref_<name>/src and built there by the revision's own Makefile
+# (make -j$MAX_JOBS, 8 by default).  The revision's Makefile must know VARIANT=; one from before
+# that builds librr_serdes.so instead, and the script stops with a message.
+# (Knob variants of the working tree: make -C redrock_old_amd/csrc VARIANT=<name> EXTRA="-D...")
 # usage: tools/build_ref.sh <rev> <name> ["-DEXTRA ..."]
 set -e
 rev=$1; name=$2; flags=$3
 root=$(cd "$(dirname "$0")/.." && pwd)
-src=$root/build/ref_$name/src; obj=$root/build/ref_$name
+src=$root/build/ref_$name/src
 rm -rf "$src"; mkdir -p "$src/redrock_old_amd/csrc" "$src/include"
 for f in $(git -C "$root" ls-tree --name-only "$rev" redrock_old_amd/csrc/ include/); do
   git -C "$root" show "$rev:$f" > "$src/$f"
 done
-make -C "$root/redrock_old_amd/csrc" >/dev/null
-cd "$src/redrock_old_amd/csrc"
-H="/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 $flags"
-$H -c rr_kernels.hip -o "$obj/k.o"
-$H -c rr_snappy.hip -o "$obj/s.o"
-B=$root/build/csrc
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$root/redrock_old_amd/librr_serdes_$name.so" "$obj/k.o" "$obj/s.o" \
-  $B/rr_api.o $B/rr_shard.o $B/rr_snappy_api.o $B/rr_rdb.o $B/rr_kv.o $B/rr_gen.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib -lm
+make -j"${MAX_JOBS:-8}" -C "$src/redrock_old_amd/csrc" VARIANT="$name" EXTRA="$flags" >/dev/null
+lib=$src/redrock_old_amd/librr_serdes_$name.so
+[ -f "$lib" ] || { echo "$rev's Makefile built no librr_serdes_$name.so (no VARIANT= support?)" >&2; exit 1; }
+cp "$lib" "$root/redrock_old_amd/"
 echo "built librr_serdes_$name.so from $rev"

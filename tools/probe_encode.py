@@ -1,5 +1,5 @@
 """Diagnostics: per-window phase times of the encode emit kernel (probe build).
-Build:  bash tools/build_variants.sh probe "-DRR_PROBE"
+Build:  make -C redrock_old_amd/csrc VARIANT=probe EXTRA=-DRR_PROBE
 Run (GPU box):  RR_LIB=librr_serdes_probe.so python tools/probe_encode.py [config] [n]"""
 import ctypes as C
 import os

@@ -1,6 +1,6 @@
 """Diagnostics: where the snappy decompressor's time goes, per LDS-path block (s_memtime cycles
 of each phase, summed over the call by the probe build's counters).
-Build:  bash tools/build_variants.sh probe "-DRR_PROBE"
+Build:  make -C redrock_old_amd/csrc VARIANT=probe EXTRA=-DRR_PROBE
 Run (GPU box):  RR_LIB=librr_serdes_probe.so python tools/probe_snappy.py [config] [n]"""
 import ctypes as C
 import os

@@ -1,4 +1,4 @@
-"""Diagnostics: device copy bandwidth of the copy kernel's shapes (rr_copy_shape, rr_kernels.hip)
+"""Diagnostics: device copy bandwidth of the copy kernel's shapes (rr_copy_shape, rr_util.hip)
 over the bench's blob size; prints TB/s (read + write bytes) per shape."""
 import ctypes as C
 import os
