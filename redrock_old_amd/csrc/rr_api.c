@@ -503,7 +503,7 @@ static int small_grow(rr_ctx *c, size_t need) {
 #define AL16(x) (((x) + 15) & ~(size_t)15)
 
 /* Wait for a one-launch kernel by its completion word in the mapped staging (signal_done in
- * rr_kernels.hip) instead of a stream synchronisation.  The stream is polled now and then, so a
+ * rr_flat_device.h) instead of a stream synchronisation.  The stream is polled now and then, so a
  * kernel that faulted (the stream reports an error) or ended without the word cannot hang it. */
 static int small_wait(rr_ctx *c, const uint32_t *flag, uint32_t seq) {
     struct timespec t0, t1;

@@ -11,14 +11,15 @@
 //   bytes in LDS (element-parallel tasks, aligned stores) and stores it coalesced.  Details at
 //   E1-E4.
 // Small batches (<= 4096 values, <= 128 KiB): one workgroup, one launch each way.
-// (The shard helpers, the copy kernel and the look-back scan are in rr_util.hip.)
+// (What decode and encode share is in rr_flat_device.h; the shard helpers, the copy kernel and the
+// look-back scan are in rr_util.hip.)
 //
 // No MFMA: this is byte/record work bounded by HBM.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
+#include "rr_flat_device.h"   // first: RR_ABLATE's default, which rr_decode_class.h tests
 #include "rr_decode_class.h"
-#include "rr_device.h"
 #include "rr_kernels.h"
 
 using namespace rr;
@@ -297,35 +298,6 @@ __device__ __forceinline__ Parsed parse_value(P b, uint64_t off, uint64_t len, r
     return r;
 }
 
-// The encode's totals: E1's and E3's per-tile partials {bad, payload, descriptors} (3 words a
-// tile), folded by E4's block 0 into the call's totals (zeroed by E1's block 0); bytes =
-// offsets[n], or UINT64_MAX when the call's error word is set (device-side failure).
-__device__ __forceinline__ void fold_totals(const uint64_t *__restrict__ stats, uint32_t ntiles,
-                                            const uint64_t *__restrict__ offsets, uint64_t n, rr_totals *out,
-                                            uint64_t *err) {
-    __shared__ uint64_t red[3][4];
-    uint64_t b = 0, p = 0, c = 0;
-    for (uint32_t t = threadIdx.x; t < ntiles; t += blockDim.x) {
-        b += stats[3 * (uint64_t)t + 0];
-        p += stats[3 * (uint64_t)t + 1];
-        c += stats[3 * (uint64_t)t + 2];
-    }
-    b = wave_sum(b);
-    p = wave_sum(p);
-    c = wave_sum(c);
-    const uint32_t w = threadIdx.x / RR_WAVE;
-    if (lane_id() == 0) { red[0][w] = b; red[1][w] = p; red[2][w] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t tb = 0, tp = 0, tc = 0;
-        for (uint32_t k = 0; k < blockDim.x / RR_WAVE; ++k) { tb += red[0][k]; tp += red[1][k]; tc += red[2][k]; }
-        if (tb) atomicAdd((unsigned long long *)&out->n_bad, (unsigned long long)tb);
-        if (tp) atomicAdd((unsigned long long *)&out->payload, (unsigned long long)tp);
-        if (tc) atomicAdd((unsigned long long *)&out->n_elems, (unsigned long long)tc);
-        out->bytes = lb_load(err) ? ~0ull : offsets[n];
-    }
-}
-
 // ---------------------------------------------------------------------------------------- decode
 // Two launches, no inter-workgroup waits (a batch of one window generation: decode_kernel's ONE
 // form alone, which does count_kernel's part in each window):
@@ -337,10 +309,9 @@ __device__ __forceinline__ void fold_totals(const uint64_t *__restrict__ stats, 
 //                     of 512 values a class sort and a slot scan in LDS, and single-class batches
 //                     (heaviest class first) walked from the stage by the waves; the window's
 //                     marked values fixed at its end, its totals added atomically.
+// (RR_ABLATE, timing-only builds with wrong results: count_kernel 5 no List stage or walk, 6 the
+// stage lands but no walk; decode_kernel's 1-4 at K3.)
 
-#ifndef RR_ABLATE   // timing-only ablations (tools/, wrong results; the decode's 1-4 below): count_kernel 5 no
-#define RR_ABLATE 0       // List stage or walk, 6 the stage lands but no walk; enc_emit_kernel 7 no header,
-#endif                    // length or decimal field writes, 8 no payload copies, 9 no decimals, 10 no task fields
 // ---- K1: reservation + class per value ------------------------------------------------
 // reserve(i) = the descriptor slots value i owns (rr_format.h): header fields only, plus the
 // length chain of a List.  Equal to the decoded count for every valid blob.
@@ -488,14 +459,6 @@ __device__ __forceinline__ void reserve_classify(P b, uint64_t L, const uint32_t
     }
 }
 
-// Block 0 also zeroes the pipeline's per-call words (look-back state, fixup header) and the
-// totals: later kernels of the same stream use them, so no separate launch is needed.
-__device__ __forceinline__ void zero_call_words(uint64_t *words, uint32_t nwords, rr_totals *tot) {
-    if (blockIdx.x != 0) return;
-    for (uint32_t k = threadIdx.x; k < nwords; k += blockDim.x) words[k] = 0;
-    if (tot && threadIdx.x < 4) reinterpret_cast<uint64_t *>(tot)[threadIdx.x] = 0;
-}
-
 // Per value: its reservation (u32; a value that would need 2^32 slots fails capacity anyway),
 // its class and first_val.  Per window: the reservations of its values summed into wtot[w], and
 // per group of WGROUP windows into gtot[w / WGROUP] (both zero on entry: the previous call's
@@ -526,7 +489,6 @@ __device__ __forceinline__ uint32_t div_win32(uint32_t o, uint32_t win, float rc
     q = rem < 0 ? q - 1 : rem >= (int32_t)win ? q + 1 : q;
     return q;
 }
-constexpr uint32_t WGROUP = 16;   // (64: ~260 same-address atomics per group sum on config 1)
 // (The sums are zero on entry without a zeroing launch: they are double-buffered, and each
 // call's count_kernel zeroes the half the previous call used.  A zeroing kernel cost ~4.5 us a
 // call, hipMemsetAsync of a size that is not a multiple of 16 bytes two fill kernels of ~4.7 us
@@ -809,34 +771,6 @@ __device__ __forceinline__ Acc run_batch(const Src &src, uint32_t c, bool active
     }
     if (active && exact) acc = exact_value(blob, 0, v, offsets, eb_v, r_v, values, elems, cap, nfix, zraw);
     return acc;
-}
-
-struct ElemV {
-    uint64_t data;
-    uint32_t len;
-    uint32_t kind;
-};
-__device__ __forceinline__ ElemV get_elem(const rr_elem *e) {
-    uint4 w = *reinterpret_cast<const uint4 *>(e);
-    return ElemV{(uint64_t)w.x | ((uint64_t)w.y << 32), w.z, w.w & 0xFF};
-}
-
-template <uint32_t NT>
-__device__ __forceinline__ uint64_t block_excl_scan(uint64_t x, uint64_t *wsum, uint64_t &total) {
-    // (the wave scan in DPP when no lane's value reaches 2^26: the wave's sum fits 32 bits)
-    const uint64_t incl = wave_incl_scan_fast(x);
-    const uint32_t wv = threadIdx.x / RR_WAVE;
-    if (lane_id() == RR_WAVE - 1) wsum[wv] = incl;
-    lds_barrier();
-    uint64_t pre = 0, t = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < NT / RR_WAVE; ++k) {
-        const uint64_t s = wsum[k];
-        pre += k < wv ? s : 0;
-        t += s;
-    }
-    total = t;
-    return pre + incl - x;
 }
 
 // ---- the fixup of marked values (end of a window) ---------------------------------------
@@ -1763,39 +1697,9 @@ __global__ __launch_bounds__(NW * RR_WAVE) __attribute__((amdgpu_waves_per_eu(DE
 // from LDS (the reference's statuses; the walks' results are the parser's by construction), the
 // fixup of marked values, and the totals — the same records, descriptors, arena and totals as
 // the pipeline, byte for byte.
-constexpr uint32_t SMALL_NT = 1024, SMALL_VPT = 4, SMALL_N = SMALL_NT * SMALL_VPT;
-constexpr uint32_t SMALL_BYTES = 128 * 1024;   // (one workgroup: up to 160 KiB of LDS)
-// batches of at most this many values: one wave per value (the class walks on a wave / the
-// whole wave emitting one value); larger ones one lane per value (the exact parser / the byte
-// emitter) — which the host takes only for values of at most SMALL_LANE_BYTES on average
-// (rr_small_decode_fits): a lane walking a 500-byte value costs ~20 us (round 4: 64 config-4
-// values took 368 us through the lane path)
-constexpr uint32_t SMALL_GW = 256;
-constexpr uint64_t SMALL_LANE_BYTES = 64;
 constexpr uint32_t SMALL_EIN = 16 * 1024;   // encode inputs up to this size staged in LDS
 constexpr uint32_t SMALL_STAGE = SMALL_BYTES + 8192;   // + the reads past a value's end; >= the fixup's LDS
 static_assert(FIX_LDS + 4 * (SMALL_NT + 1) <= SMALL_STAGE, "the fixup reuses the stage");
-
-// The host entry points wait for a one-launch kernel by spinning on a word of their mapped
-// staging instead of a stream synchronisation (~4 us less per call).  The producer form of
-// MI355X_MICROARCH.md (inter-workgroup visibility, "valid forms"): every wave waits for its
-// OWN stores to be acknowledged (s_waitcnt vmcnt(0): on gfx950 __syncthreads() is a bare
-// s_barrier that waits for nothing in flight), then the barrier, so lane 0 signals only after
-// every wave's records, descriptors and totals have landed; lane 0's ONE system-scope release
-// (one L2 writeback), an explicit vmcnt(0) wait after it (the compiler may drop its own wait
-// after the writeback when the scoreboard looks empty), and the store of the call's sequence
-// number.  (A system fence in every thread — sixteen waves, sixteen L2 writebacks — cost ~8 us
-// a call: tools/micro/lat_probe.hip, launch + spin 19.4 us against 11.4 us between HIP events.)
-__device__ __forceinline__ void signal_done(uint32_t *done, uint32_t seq) {
-    if (!done) return;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");   // (system scope)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(done, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
 
 __global__ __launch_bounds__(SMALL_NT) void decode_small_kernel(const uint8_t *__restrict__ blob,
                                                                 const uint64_t *__restrict__ offsets, uint64_t n,
@@ -1932,6 +1836,35 @@ __global__ __launch_bounds__(SMALL_NT) void decode_small_kernel(const uint8_t *_
 }
 
 // ---------------------------------------------------------------------------------------- encode
+// The encode's totals: E1's and E3's per-tile partials {bad, payload, descriptors} (3 words a
+// tile), folded by E4's block 0 into the call's totals (zeroed by E1's block 0); bytes =
+// offsets[n], or UINT64_MAX when the call's error word is set (device-side failure).
+__device__ __forceinline__ void fold_totals(const uint64_t *__restrict__ stats, uint32_t ntiles,
+                                            const uint64_t *__restrict__ offsets, uint64_t n, rr_totals *out,
+                                            uint64_t *err) {
+    __shared__ uint64_t red[3][4];
+    uint64_t b = 0, p = 0, c = 0;
+    for (uint32_t t = threadIdx.x; t < ntiles; t += blockDim.x) {
+        b += stats[3 * (uint64_t)t + 0];
+        p += stats[3 * (uint64_t)t + 1];
+        c += stats[3 * (uint64_t)t + 2];
+    }
+    b = wave_sum(b);
+    p = wave_sum(p);
+    c = wave_sum(c);
+    const uint32_t w = threadIdx.x / RR_WAVE;
+    if (lane_id() == 0) { red[0][w] = b; red[1][w] = p; red[2][w] = c; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t tb = 0, tp = 0, tc = 0;
+        for (uint32_t k = 0; k < blockDim.x / RR_WAVE; ++k) { tb += red[0][k]; tp += red[1][k]; tc += red[2][k]; }
+        if (tb) atomicAdd((unsigned long long *)&out->n_bad, (unsigned long long)tb);
+        if (tp) atomicAdd((unsigned long long *)&out->payload, (unsigned long long)tp);
+        if (tc) atomicAdd((unsigned long long *)&out->n_elems, (unsigned long long)tc);
+        out->bytes = lb_load(err) ? ~0ull : offsets[n];
+    }
+}
+
 __device__ __forceinline__ bool fits_width(int64_t x, uint32_t w) {
     if (w == 8) return true;
     if (w == 4) return x >= INT32_MIN && x <= INT32_MAX;
@@ -1963,8 +1896,6 @@ struct ElemCost {
     uint64_t bytes, pay;
     bool bad;
 };
-// a STR / ZLRAW descriptor's payload lies inside the caller's arena
-__device__ __forceinline__ bool in_arena(const ElemV &e, uint64_t acap) { return e.data <= acap && e.len <= acap - e.data; }
 __device__ __forceinline__ ElemCost elem_cost(uint32_t type, uint32_t enc, uint64_t i, const ElemV &e, uint64_t acap) {
     switch (type) {
         case RR_TYPE_LIST_QUICKLIST:
@@ -2403,6 +2334,8 @@ __global__ __launch_bounds__(256) void enc_index_kernel(const rr_value *__restri
 //   SET/HASH HT  h=13 (+ u64 count)            8 + len
 //   ZIPLIST   h=5,  one task (descriptor 0, the raw ziplist): 8 + len
 //   SKIPLIST  h=13 (+ u64 count)               member: 8 + len        score: 8 (raw f64)
+// (RR_ABLATE, timing-only builds with wrong results: enc_emit_kernel 7 no header, length or decimal
+// field writes, 8 no payload copies, 9 no decimals, 10 no task fields.)
 __device__ __forceinline__ uint32_t enc_hdr(uint32_t type) {
     return type == RR_TYPE_STRING ? 6u : (type == RR_TYPE_LIST_QUICKLIST || type == RR_TYPE_HASH_ZIPLIST ||
                                           type == RR_TYPE_ZSET_ZIPLIST) ? 5u : 13u;
@@ -3319,15 +3252,15 @@ static bool dec_one(void) {
     return v != 0;
 }
 
-// Resident workgroup count for a persistent launch: occupancy query minus one block per CU
-// (the API over-reports by one for SGPR-heavy kernels, MI355X_MICROARCH.md §Residency).
+// Resident workgroup count of a kernel, as the occupancy query gives it (a persistent launch would
+// take one block per CU off: the API over-reports by one for SGPR-heavy kernels,
+// MI355X_MICROARCH.md §Residency).
 template <typename K>
-static uint32_t resident_grid(K kernel, int block, bool margin = true) {
+static uint32_t resident_grid(K kernel, int block) {
     int dev = 0, cus = 0, occ = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, block, 0) != hipSuccess || occ < 1) occ = 1;
-    if (margin && occ > 1) occ -= 1;
     if (cus < 1) cus = 1;
     return (uint32_t)(cus * occ);
 }
@@ -3355,7 +3288,7 @@ static uint32_t dev_cache(uint32_t (&cache)[RR_MAX_DEV], uint32_t (*query)(void)
     }
     return v;
 }
-static uint32_t q_dec_slots(void) { return resident_grid(DECODE_KERNEL, DEC_NW * RR_WAVE, false); }
+static uint32_t q_dec_slots(void) { return resident_grid(DECODE_KERNEL, DEC_NW * RR_WAVE); }
 static uint32_t q_cus(void) {
     int dev = 0, c = 0;
     (void)hipGetDevice(&dev);

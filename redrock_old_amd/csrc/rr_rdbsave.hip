@@ -18,6 +18,7 @@
 // back when it opens the node, writes the prefix and places the entries behind it.
 #include <hip/hip_runtime.h>
 
+#include "rr_flat_device.h"
 #include "rr_rdb_device.h"
 #include "rr_kernels.h"
 
@@ -29,16 +30,6 @@ constexpr uint32_t WPB = 4;             // waves (values in flight) per workgrou
 constexpr uint32_t GRID_CAP = 16384;    // workgroups: 65536 waves, 256 per CU on 256 CUs (8 rounds of 32 resident)
 constexpr uint32_t LIST_GROUP = 8;      // values a wave of rdb_list_kernel looks at per step
 constexpr uint32_t SHORT_BODY = 32;     // a body of up to this many bytes is copied by its own lane
-
-struct ElemV {
-    uint64_t data;
-    uint32_t len, kind;
-};
-__device__ __forceinline__ ElemV get_elem(const rr_elem *e) {
-    const uint4 x = *reinterpret_cast<const uint4 *>(e);
-    return {(uint64_t)x.x | ((uint64_t)x.y << 32), x.z, x.w & 0xFF};
-}
-__device__ __forceinline__ bool in_arena(const ElemV &e, uint64_t acap) { return e.data <= acap && e.len <= acap - e.data; }
 
 // Wave64 inclusive scan of costs below 2^40 (a cost is at most 2^32 + 8), every lane active: the low
 // 24 bits and the rest scanned apart by the u32 DPP scan, which needs no per-step lane predicates

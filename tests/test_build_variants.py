@@ -1,4 +1,4 @@
-"""Every compile-time knob the kernel sources keep (rr_kernels.hip, rr_util.hip,
+"""Every compile-time knob the kernel sources keep (rr_kernels.hip, rr_flat_device.h, rr_util.hip,
 rr_decode_class.h, rr_snappy.hip) still compiles for gfx950 with a non-default value, so no kept
 path rots: a front-end pass (templates instantiated, static_asserts checked) of each variant's device code.
 The default build is compiled in full by __graft_entry__.build().  CPU only (hipcc
@@ -51,7 +51,8 @@ def _knobs(src):
 
 def test_every_knob_has_a_variant():
     """The variant list covers every RR_* knob the sources test (and they stay few)."""
-    knobs = _knobs("rr_kernels.hip") | _knobs("rr_util.hip") | _knobs("rr_decode_class.h") | _knobs("rr_snappy.hip")
+    knobs = set().union(*map(_knobs, ("rr_kernels.hip", "rr_flat_device.h", "rr_util.hip", "rr_decode_class.h",
+                                      "rr_snappy.hip")))
     covered = set(re.findall(r"-D(RR_[A-Z0-9_]+)", " ".join(f for _, f in VARIANTS)))
     assert knobs <= covered, sorted(knobs - covered)
     assert len(knobs) <= 16, sorted(knobs)

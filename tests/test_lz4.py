@@ -132,7 +132,7 @@ def test_every_lz4_knob_has_a_variant():
     knobs = set(re.findall(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b.*?\b(RR_[A-Z0-9_]+)", text, re.M))
     assert knobs and all(k.startswith("RR_LZ4_") for k in knobs), knobs
     assert knobs <= set(re.findall(r"-D(RR_[A-Z0-9_]+)", " ".join(VARIANTS)))
-    for other in ("rr_kernels.hip", "rr_util.hip", "rr_decode_class.h", "rr_snappy.hip"):
+    for other in ("rr_kernels.hip", "rr_flat_device.h", "rr_util.hip", "rr_decode_class.h", "rr_snappy.hip"):
         assert "RR_LZ4_" not in open(os.path.join(CSRC, other)).read(), other
 
 
