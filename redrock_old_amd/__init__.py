@@ -147,6 +147,11 @@ RDBLOAD_EXPORTS = ["rr_rdbload_bound", "rr_rdbload_batch", "rr_rdbload_batch_hos
 RDBLOAD_E_TYPE, RDBLOAD_E_LEN, RDBLOAD_E_TRUNC, RDBLOAD_E_LZF = 32, 33, 34, 35
 RDBLOAD_E_EXTRA, RDBLOAD_E_ZIPLIST, RDBLOAD_E_CONVERT = 36, 37, 38
 RDBLOAD_LZF_NODE_MAX = 10240    # the longest List node taken in the LZF form
+# include/rr_rdbconvert.h (the values rdbload left with RDBLOAD_E_CONVERT, in the encoding rdbLoadObject picks)
+RDBCONVERT_EXPORTS = ["rr_rdbconvert_bound", "rr_rdbconvert_batch", "rr_rdbconvert_batch_host"]
+RDBCONVERT_SKIP = 45            # not attempted: load_status != RDBLOAD_E_CONVERT
+RDBCONVERT_MAX_N = 512          # the most members of a Set or ZSet that is sorted
+RDBCONVERT_MAX_WAVES = 16384    # a wave an attempted value, a grid stride beyond
 # include/rr_rdbfile.h (RDB stream framing, DUMP payloads and their CRC-64 around the payloads above)
 RDBFILE_EXPORTS = ["rr_rdbfile_bound", "rr_rdbfile_section", "rr_rdbfile_section_host", "rr_crc64_device",
                    "rr_rdbdump_batch", "rr_rdbdump_batch_host", "rr_rdbdump_verify_batch", "rr_rdbdump_verify_batch_host",
@@ -246,6 +251,13 @@ def lib():
         L.rr_rdbload_bound.restype = u64
         L.rr_rdbload_batch.argtypes = [vp, C.POINTER(BlobBatch), vp, C.POINTER(BlobBatch), vp, vp, C.POINTER(RdbLoadOpts), vp]
         L.rr_rdbload_batch_host.argtypes = [vp, vp, vp, vp, u64, C.POINTER(RdbLoadOpts), vp, u64, vp, vp, C.POINTER(Totals)]
+    if "RR_LIB" not in os.environ or hasattr(L, "rr_rdbconvert_batch"):   # (RR_LIB: an older build may predate them)
+        L.rr_rdbconvert_bound.argtypes = [u64, u64]
+        L.rr_rdbconvert_bound.restype = u64
+        L.rr_rdbconvert_batch.argtypes = [vp, C.POINTER(BlobBatch), vp, vp, C.POINTER(BlobBatch), vp, vp, vp,
+                                          C.POINTER(RdbLoadOpts), vp]
+        L.rr_rdbconvert_batch_host.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(RdbLoadOpts), vp, u64, vp, vp, vp,
+                                               C.POINTER(Totals)]
     if "RR_LIB" not in os.environ or hasattr(L, "rr_rdbfile_section"):   # (RR_LIB: an older build may predate them)
         L.rr_rdbfile_bound.argtypes = [u64, u64, u64, u64]
         L.rr_rdbfile_bound.restype = u64
@@ -717,6 +729,42 @@ class Engine:
                                         C.c_void_p(status.data_ptr()), C.c_void_p(totals.data_ptr()),
                                         C.byref(opts) if opts is not None else None, _sp(stream)))
 
+    # ---- the encodings rdbLoadObject picks for RDBLOAD_E_CONVERT values (include/rr_rdbconvert.h) ----
+    def rdbconvert_host(self, data: np.ndarray, offsets: np.ndarray, types: np.ndarray, load_status: np.ndarray,
+                        opts: RdbLoadOpts | None = None, out_cap: int | None = None):
+        """RDB payloads and rdbload's status -> (blob data, offsets, out_types, status, totals): the blobs of
+        the values rdbload left with RDBLOAD_E_CONVERT.  out_cap None: asks for the size first."""
+        n = len(offsets) - 1
+        data = np.ascontiguousarray(data, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        types = np.ascontiguousarray(types, np.uint8)
+        load_status = np.ascontiguousarray(load_status, np.uint8)
+        out_offsets = np.zeros(n + 1, np.uint64)
+        out_types = np.zeros(max(n, 1), np.uint8)
+        status = np.zeros(max(n, 1), np.uint8)
+        t = Totals()
+        po = C.byref(opts) if opts is not None else None
+        if out_cap is None:
+            _check(self._L.rr_rdbconvert_batch_host(self._ctx, _ptr(data), _ptr(offsets), _ptr(types), _ptr(load_status), n, po,
+                                                    None, 0, _ptr(out_offsets), _ptr(out_types), _ptr(status), C.byref(t)))
+            out_cap = int(out_offsets[-1])
+        out = np.zeros(max(out_cap, 1), np.uint8)
+        _check(self._L.rr_rdbconvert_batch_host(self._ctx, _ptr(data), _ptr(offsets), _ptr(types), _ptr(load_status), n, po,
+                                                _ptr(out), out_cap, _ptr(out_offsets), _ptr(out_types), _ptr(status),
+                                                C.byref(t)))
+        return out[:min(int(out_offsets[-1]), out_cap)], out_offsets, out_types[:n], status[:n], t.as_dict()
+
+    def rdbconvert(self, data, offsets, types, load_status, out_data, out_offsets, out_types, status, totals,
+                   opts: RdbLoadOpts | None = None, stream=None):
+        """rr_rdbconvert_batch on torch CUDA tensors; no host sync.  out_data may be empty (sizes only)."""
+        n = out_offsets.numel() - 1
+        inb = BlobBatch(data.data_ptr() if data.numel() else None, offsets.data_ptr(), n, data.numel())
+        outb = BlobBatch(out_data.data_ptr() if out_data.numel() else None, out_offsets.data_ptr(), n, out_data.numel())
+        _check(self._L.rr_rdbconvert_batch(self._ctx, C.byref(inb), C.c_void_p(types.data_ptr()),
+                                           C.c_void_p(load_status.data_ptr()), C.byref(outb), C.c_void_p(out_types.data_ptr()),
+                                           C.c_void_p(status.data_ptr()), C.c_void_p(totals.data_ptr()),
+                                           C.byref(opts) if opts is not None else None, _sp(stream)))
+
     # ---- RDB streams and DUMP payloads with their CRC-64 (include/rr_rdbfile.h) -------------------
     def rdbfile_section(self, pay_data, pay_offsets, types, status, key_data, key_offsets, out, rec_offsets, rec_status,
                         state, result, expires=None, idle=None, freq=None, head=None, flags: int = 0, stream=None,
@@ -893,6 +941,11 @@ def rdbsave_bound(values: np.ndarray, elems: np.ndarray) -> int:
 def rdbload_bound(n: int, payload_bytes: int) -> int:
     """rr_rdbload_bound: an upper bound on the blob bytes of n payloads without LZF strings."""
     return int(lib().rr_rdbload_bound(n, payload_bytes))
+
+
+def rdbconvert_bound(n: int, payload_bytes: int) -> int:
+    """rr_rdbconvert_bound: an upper bound on the blob bytes of n converted payloads without LZF strings."""
+    return int(lib().rr_rdbconvert_bound(n, payload_bytes))
 
 
 # ---- include/rr_rdbfile.h: the host helpers (no GPU) ---------------------------------------------

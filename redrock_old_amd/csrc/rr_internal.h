@@ -76,6 +76,11 @@ RR_HIDDEN int rr_check_blob_io(const rr_ctx *c, const rr_blob_batch *in, const r
  * look-back's error mark, then brings down the first min(*bytes, cap) bytes of the output. */
 RR_HIDDEN int rr_host_finish(rr_ctx *c, const char *name, const uint64_t *bytes, void *out, const void *d_out, uint64_t cap);
 
+/* rr_rdbload_opts checked and resolved (NULL: the defaults) into what the RDB load kernels take: lru &
+ * RR_LRU_MASK, then the five thresholds.  Sets the error.  (rr_rdbload_api.c) */
+struct rr_rdbload_opts;
+RR_HIDDEN int rr_rdbload_resolve_opts(const struct rr_rdbload_opts *o, uint32_t k[6]);
+
 /* read / write exactly len bytes on a blocking fd: 1 done, 0 closed, -1 error
  * (the reference's _read_pipe_by_length / _write_pipe_by_length, rock_rdb.c:64-103) */
 RR_HIDDEN int rr_read_full(int fd, void *buf, size_t len);

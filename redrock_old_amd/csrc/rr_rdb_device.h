@@ -1,5 +1,5 @@
 // rr_rdb_device.h — the RDB wire format's lengths and integers, shared by the RDB kernels
-// (rr_rdbsave.hip, rr_rdbload.hip, rr_rdbfile.hip).  Line references are to the reference's rdb.c.
+// (rr_rdbsave.hip, rr_rdbload.hip, rr_rdbconvert.hip, rr_rdbfile.hip).  Line references are to the reference's rdb.c.
 #pragma once
 #include "rr_device.h"
 
@@ -43,5 +43,16 @@ __device__ __forceinline__ void put_rint(uint8_t *d, int64_t v) {
 __device__ __forceinline__ bool raw_is_int(const uint8_t *s, uint32_t len, int64_t &v) {
     return len <= 11 && zip_try_int(s, len, v) && is_i32(v);
 }
+// ---- ziplist entries (ziplist.c:332-364, :480-534): an integer entry's data bytes and encoding byte, a
+// string entry's header bytes ----
+__device__ __forceinline__ uint32_t zint_bytes(int64_t v) {
+    return v >= 0 && v <= 12 ? 0u : v >= -128 && v <= 127 ? 1u : v >= -32768 && v <= 32767 ? 2u
+         : v >= -8388608 && v <= 8388607 ? 3u : is_i32(v) ? 4u : 8u;
+}
+__device__ __forceinline__ uint32_t zint_enc(int64_t v) {
+    const uint32_t nb = zint_bytes(v);
+    return nb == 0 ? 0xF1u + (uint32_t)v : nb == 1 ? 0xFEu : nb == 2 ? 0xC0u : nb == 3 ? 0xF0u : nb == 4 ? 0xD0u : 0xE0u;
+}
+__device__ __forceinline__ uint32_t zstr_hdr(uint32_t len) { return len <= 0x3F ? 1u : len <= 0x3FFF ? 2u : 5u; }
 
 }  // namespace rr

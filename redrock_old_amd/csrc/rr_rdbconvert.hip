@@ -1,0 +1,504 @@
+// rr_rdbconvert.hip — gfx950 kernels of include/rr_rdbconvert.h: the values rr_rdbload_batch left
+// with RR_RDBLOAD_E_CONVERT, in the encoding rdbLoadObject picks for them (rdb.c:1476-1600): a Set of
+// integers as an intset, a small Hash and a small ZSet as ziplists.  Six launches:
+// rdbconvert_flag_kernel (a thread a value: which values are attempted, RR_RDBCONVERT_SKIP for the
+// rest, and the zeroing the other launches rely on), rr_launch_scan_u64, rdbconvert_compact_kernel
+// (the attempted values' indices, in order), rdbconvert_size_kernel (every decision and the blob
+// sizes), rr_launch_scan_u64, rdbconvert_emit_kernel (the bytes, RR_E_CAPACITY, the totals).
+//
+// The attempted values are the rare class of a batch, so the size and emit passes run over the
+// compacted list, a wave per value, at most RR_RDBCONVERT_MAX_WAVES waves a launch and a grid stride
+// beyond.  The walk is rr_rdbload.hip's (rr_rdbload_device.h): wave-uniform, every load of payload
+// bytes in the size pass through a buffer resource over exactly the value's slice, so a value that
+// is not what its load_status claims reads zeros, never a neighbour, and ends as E_CONVERT.
+//
+// Sorting is a rank sort in the wave's LDS: element i goes to the slot that is the number of
+// elements before it in the order (ties by index, so the ranks are a permutation); a lane an
+// element, every lane reading the same other element at a time (an LDS broadcast).  n is at most
+// RR_RDBCONVERT_MAX_N, so that is 8 elements a lane and n reads each.  A Set sorts its int64 values
+// and drops the duplicates behind it; a ZSet sorts (score, member) with a table of member offsets
+// and lengths, the member bytes compared in the payload when scores tie.  Both passes sort: the size
+// pass needs the intset's length and width and the ziplist's prevlen chain, and a permutation kept in
+// scratch for the emit pass would cost what the second sort costs.
+#include <hip/hip_runtime.h>
+
+#include "rr_rdbload_device.h"
+#include "rr_kernels.h"
+#include "../../include/rr_rdbconvert.h"
+
+using namespace rr;
+
+namespace {
+
+constexpr uint32_t WPB = 4;                            // waves (values in flight) per workgroup
+constexpr uint32_t MAXN = RR_RDBCONVERT_MAX_N;
+constexpr uint32_t GRID_CAP = RR_RDBCONVERT_MAX_WAVES / WPB;   // workgroups
+constexpr uint32_t PEEK = 64;                          // the wave's window: a string's first bytes only
+constexpr uint32_t INTF = 0x80000000u;                 // mlen[]: the member is in the integer form, moff[] its value
+// a wave's LDS: key[MAXN] u64 | moff[MAXN] u32, mlen[MAXN] u32 (a Set: sorted[MAXN] i64) | ord[MAXN] u16 | window
+constexpr uint32_t WAVE_LDS = 8 * MAXN + 8 * MAXN + 2 * MAXN + PEEK;
+static_assert(WPB * WAVE_LDS <= 65536 && WAVE_LDS % 8 == 0 && MAXN <= 65535 && PEEK >= RR_WAVE, "static LDS");
+static_assert(RR_RDBCONVERT_MAX_WAVES % WPB == 0, "whole workgroups");
+
+struct Lds {
+    lds_u64 *key;      // a Set's values; a ZSet's score bits
+    lds_u64 *sorted;   // a Set's values in order (over moff / mlen)
+    lds_u32 *moff, *mlen;
+    lds_u16 *ord;      // a ZSet's permutation: ord[rank] = index
+    lds_u8 *win;
+};
+
+__device__ __forceinline__ Lds wave_lds() {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[WPB * WAVE_LDS];
+    lds_u8 *b = (lds_u8 *)lds + (threadIdx.x / RR_WAVE) * WAVE_LDS;
+    return {(lds_u64 *)b, (lds_u64 *)(b + 8 * MAXN), (lds_u32 *)(b + 8 * MAXN), (lds_u32 *)(b + 12 * MAXN),
+            (lds_u16 *)(b + 16 * MAXN), b + 18 * MAXN};
+}
+
+// what other lanes of the wave wrote to LDS is read after this (a wave's LDS operations complete in
+// order; this keeps the compiler from moving them)
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// ---- the ziplist under construction (ziplist.c:743-839 at the tail) -------------------------------
+struct Zl {
+    uint64_t pos;    // where the next entry starts
+    uint64_t prev;   // the last entry's whole size
+    uint64_t last;   // the last entry's offset (zltail)
+};
+// zipStorePrevEntryLength (ziplist.c:408-419); returns where the encoding starts
+template <bool EMIT>
+__device__ __forceinline__ uint64_t zl_prevlen(const Zl &z, uint8_t *zb) {
+    const uint32_t pls = z.prev < 254 ? 1 : 5;
+    if (EMIT && lane_id() == 0) {
+        if (pls == 1) zb[z.pos] = (uint8_t)z.prev;
+        else {
+            zb[z.pos] = 0xFE;
+            put_le(zb + z.pos + 1, z.prev, 4);
+        }
+    }
+    return z.pos + pls;
+}
+__device__ __forceinline__ void zl_advance(Zl &z, uint64_t end) {
+    z.prev = end - z.pos;
+    z.last = z.pos;
+    z.pos = end;
+}
+// an integer entry (zipTryEncoding's choice :487-498, zipSaveInteger :507-534)
+template <bool EMIT>
+__device__ __forceinline__ void zl_push_int(Zl &z, uint8_t *zb, int64_t v) {
+    const uint64_t q = zl_prevlen<EMIT>(z, zb);
+    const uint32_t nb = zint_bytes(v);
+    if (EMIT && lane_id() == 0) {
+        zb[q] = (uint8_t)zint_enc(v);
+        put_le(zb + q + 1, (uint64_t)v, nb);
+    }
+    zl_advance(z, q + 1 + nb);
+}
+// a string entry's prevlen and header (zipStoreEntryEncoding :332-364); returns where its bytes go.
+// The caller places them and then calls zl_advance(z, that + len).
+template <bool EMIT>
+__device__ __forceinline__ uint64_t zl_str_hdr(const Zl &z, uint8_t *zb, uint32_t len) {
+    const uint64_t q = zl_prevlen<EMIT>(z, zb);
+    const uint32_t h = zstr_hdr(len);
+    if (EMIT && lane_id() == 0) {
+        if (h == 1) zb[q] = (uint8_t)len;
+        else if (h == 2) {
+            zb[q] = (uint8_t)(0x40 | (len >> 8));
+            zb[q + 1] = (uint8_t)len;
+        } else {
+            zb[q] = 0x80;
+            put_be(zb + q + 1, len, 4);
+        }
+    }
+    return q + h;
+}
+// ziplistPush of a loaded string: zipTryEncoding (:480-504) first.  The integer form is ll2string's
+// text, which string2ll takes back; a string of more than 20 bytes cannot pass string2ll.
+template <bool EMIT>
+__device__ __forceinline__ void zl_push(const Rd &r, const Str &s, Zl &z, uint8_t *zb, lds_u8 *win) {
+    int64_t iv = s.iv;
+    bool isint = s.kind == S_INT;
+    if (!isint && s.len >= 1 && s.len <= 20) isint = str_is_ll(r, materialize(r, s, 20, win), s.len, win, iv);
+    if (isint) {
+        zl_push_int<EMIT>(z, zb, iv);
+        return;
+    }
+    const uint64_t d = zl_str_hdr<EMIT>(z, zb, s.len);
+    if (EMIT) emit_string(r, s, zb + d);
+    zl_advance(z, d + s.len);
+}
+
+// ---- scores ----------------------------------------------------------------------------------------
+// d2string (util.c:517-552) without its %.17g branch: 0 not taken (NaN, or a score for :548), 1 the
+// integer iv (ll2string :545; +0 is "0" :530), 2 "inf", 3 "-inf" (:521-524), 4 "-0" (:528)
+enum : uint32_t { SC_NO = 0, SC_INT = 1, SC_INF = 2, SC_NINF = 3, SC_NZERO = 4 };
+__device__ __forceinline__ uint32_t score_class(uint64_t bits, int64_t &iv) {
+    const uint64_t mag = bits & 0x7FFFFFFFFFFFFFFFull;
+    iv = 0;
+    if (mag > 0x7FF0000000000000ull) return SC_NO;
+    if (mag == 0x7FF0000000000000ull) return bits >> 63 ? SC_NINF : SC_INF;
+    if (mag == 0) return bits >> 63 ? SC_NZERO : SC_INT;
+    const double d = __longlong_as_double((long long)bits);
+    if (!(d > -4503599627370495.0 && d < 4503599627370496.0)) return SC_NO;   // :542-544
+    const long long t = (long long)d;
+    if ((double)t != d) return SC_NO;
+    iv = t;
+    return SC_INT;
+}
+// the order of doubles (no NaN) as the order of unsigned integers, -0 with 0
+__device__ __forceinline__ uint64_t score_key(uint64_t bits) {
+    if ((bits << 1) == 0) bits = 0;
+    return bits >> 63 ? ~bits : bits | (1ull << 63);
+}
+
+// ---- members, for the tie compare (per lane, each lane its own pair) --------------------------------
+// an integer-form member's text (ll2string of an int32: at most 11 bytes), byte k at bits 8k
+struct Txt {
+    uint64_t lo, hi;
+};
+__device__ __forceinline__ Txt int_text(int32_t v, uint32_t len) {
+    Txt t = {0, 0};
+    uint64_t a = v < 0 ? 0ull - (uint64_t)(int64_t)v : (uint64_t)v;
+    uint32_t q = len;
+    do {
+        --q;
+        const uint64_t c = '0' + a % 10;
+        if (q < 8) t.lo |= c << (8 * q);
+        else t.hi |= c << (8 * (q - 8));
+        a /= 10;
+    } while (a && q);
+    if (v < 0) t.lo = (t.lo & ~0xFFull) | '-';
+    return t;
+}
+__device__ __forceinline__ uint32_t member_byte(rsrc_t R, uint32_t off, bool isint, const Txt &t, uint32_t k) {
+    if (isint) return (uint32_t)((k < 8 ? t.lo >> (8 * k) : t.hi >> (8 * (k & 7))) & 0xFF);
+    return ld8(R, off + k);
+}
+// sdscmp (sds.c:792-802) of members a and b: < 0, 0, > 0
+__device__ __forceinline__ int member_cmp(rsrc_t R, uint32_t ao, uint32_t al, uint32_t bo, uint32_t bl) {
+    const bool ai = al & INTF, bi = bl & INTF;
+    al &= ~INTF;
+    bl &= ~INTF;
+    const Txt ta = ai ? int_text((int32_t)ao, al) : Txt{0, 0}, tb = bi ? int_text((int32_t)bo, bl) : Txt{0, 0};
+    const uint32_t m = al < bl ? al : bl;
+    for (uint32_t k = 0; k < m; ++k) {
+        const uint32_t ca = member_byte(R, ao, ai, ta, k), cb = member_byte(R, bo, bi, tb, k);
+        if (ca != cb) return ca < cb ? -1 : 1;
+    }
+    return al < bl ? -1 : al > bl ? 1 : 0;
+}
+
+// ---- one value -------------------------------------------------------------------------------------
+// Returns the blob's size, with status RR_OK and the new type (size pass), or writes the blob at out
+// (EMIT, a value the size pass converted).  Anything else: status RR_RDBLOAD_E_CONVERT, size 0.
+// pay / nel: rr_totals.payload and n_elems of this value, added.
+template <bool EMIT>
+__device__ uint64_t convert_value(Rd &r, uint32_t type, const Opt &O, const Lds &W, uint8_t *out, uint32_t &status, uint32_t &otype,
+                                  uint64_t &pay, uint64_t &nel) {
+    const uint32_t lane = lane_id();
+    status = RR_RDBLOAD_E_CONVERT;
+    otype = 0;
+    if (type != RR_TYPE_SET_HT && type != RR_TYPE_HASH_HT && type != RR_TYPE_ZSET_SKIPLIST) return 0;
+    if (r.p >= r.n) return 0;
+    const uint32_t hv = ld8(r.R, r.p + lane);
+    bool ie;
+    uint64_t n;
+    uint32_t used;
+    if (parse_len(hv, 0, r.n - r.p, ie, n, used)) return 0;   // a count site
+    r.p += used;
+    Str s;
+    uint64_t size;
+    if (type == RR_TYPE_SET_HT) {                              // rdb.c:1481-1506
+        if (n > O.set_ie || n > MAXN) return 0;
+        const uint32_t cnt_in = (uint32_t)n;
+        for (uint32_t k = 0; k < cnt_in; ++k) {
+            if (rd_string<!EMIT>(r, s)) return 0;
+            int64_t v = s.iv;
+            if (s.kind != S_INT && !(s.len >= 1 && s.len <= 20 && str_is_ll(r, materialize(r, s, 20, W.win), s.len, W.win, v)))
+                return 0;                                      // isSdsRepresentableAsLongLong :1501
+            if (lane == 0) W.key[k] = (uint64_t)v;
+        }
+        if (r.p != r.n) return 0;
+        wave_sync();
+        for (uint32_t i = lane; i < cnt_in; i += RR_WAVE) {    // intsetSearch's slot for every value at once
+            const int64_t ki = (int64_t)W.key[i];
+            uint32_t rank = 0;
+            for (uint32_t j = 0; j < cnt_in; ++j) {
+                const int64_t kj = (int64_t)W.key[j];
+                rank += (kj < ki || (kj == ki && j < i)) ? 1u : 0u;
+            }
+            W.sorted[rank] = (uint64_t)ki;
+        }
+        wave_sync();
+        uint32_t enc = 2;                                      // intsetNew; _intsetValueEncoding of the extremes
+        if (cnt_in) {
+            const int64_t lo = (int64_t)first64(W.sorted[0]), hi = (int64_t)first64(W.sorted[cnt_in - 1]);
+            enc = (lo < -2147483648ll || hi > 2147483647ll) ? 8u : (lo < -32768 || hi > 32767) ? 4u : 2u;
+        }
+        uint32_t cnt = 0;
+        for (uint32_t b = 0; b < cnt_in; b += RR_WAVE) {       // a value already there is dropped (intset.c:219)
+            const uint32_t k = b + lane;
+            const bool in = k < cnt_in;
+            const uint64_t vk = in ? W.sorted[k] : 0;
+            const bool uniq = in && (k == 0 || W.sorted[k - 1] != vk);
+            const uint64_t m = __ballot(uniq);
+            if (EMIT && uniq) put_le(out + 13 + (uint64_t)(cnt + __popcll(m & ((1ull << lane) - 1))) * enc, vk, enc);
+            cnt += (uint32_t)__popcll(m);
+        }
+        if (EMIT && lane == 0) {
+            put_le(out + 5, enc, 4);
+            put_le(out + 9, cnt, 4);
+        }
+        otype = RR_TYPE_SET_INTSET;
+        size = 13 + (uint64_t)enc * cnt;
+        pay += 8 + (uint64_t)enc * cnt;
+        nel += cnt_in;
+        wave_sync();   // the next value's keys go over these
+    } else {
+        Zl z = {10, 0, 10};
+        uint8_t *zb = out + 13;
+        uint32_t entries;
+        if (type == RR_TYPE_HASH_HT) {                         // rdb.c:1567-1596
+            if (n > O.hash_e) return 0;
+            entries = 2 * (uint32_t)n;
+            for (uint32_t k = 0; k < entries; ++k) {
+                if (rd_string<!EMIT>(r, s)) return 0;
+                if (s.len > O.hash_v) return 0;                // :1586
+                zl_push<EMIT>(r, s, z, zb, W.win);
+            }
+            if (r.p != r.n) return 0;
+            nel += entries;
+            otype = RR_TYPE_HASH_ZIPLIST;
+        } else {                                               // rdb.c:1517-1555
+            if (n > O.zset_e || n > MAXN) return 0;
+            const uint32_t cnt_in = (uint32_t)n;
+            entries = 2 * cnt_in;
+            for (uint32_t k = 0; k < cnt_in; ++k) {
+                if (rd_string<!EMIT>(r, s)) return 0;
+                if (s.kind == S_LZF || s.len > O.zset_v) return 0;
+                if (r.n - r.p < 8) return 0;
+                const uint64_t bits = le_lanes(ld8(r.R, r.p + lane), 0, 8);   // rdbLoadBinaryDoubleValue
+                r.p += 8;
+                int64_t iv;
+                if (score_class(bits, iv) == SC_NO) return 0;
+                if (lane == 0) {
+                    W.key[k] = bits;
+                    W.moff[k] = s.kind == S_INT ? (uint32_t)(int32_t)s.iv : s.off;
+                    W.mlen[k] = s.len | (s.kind == S_INT ? INTF : 0u);
+                }
+            }
+            if (r.p != r.n) return 0;
+            wave_sync();
+            for (uint32_t i = lane; i < cnt_in; i += RR_WAVE) {    // zslInsert's order (t_zset.c:142-145)
+                const uint64_t ki = score_key(W.key[i]);
+                const uint32_t io = W.moff[i], il = W.mlen[i];
+                uint32_t rank = 0;
+                for (uint32_t j = 0; j < cnt_in; ++j) {
+                    const uint64_t kj = score_key(W.key[j]);
+                    bool before = kj < ki;
+                    if (kj == ki && j != i) {
+                        const int c = member_cmp(r.R, W.moff[j], W.mlen[j], io, il);
+                        before = c < 0 || (c == 0 && j < i);
+                    }
+                    rank += before ? 1u : 0u;
+                }
+                W.ord[rank] = (uint16_t)i;
+            }
+            wave_sync();
+            for (uint32_t k = 0; k < cnt_in; ++k) {                // zsetConvert :1221-1230, zzlInsertAt :1035-1038
+                const uint32_t i = rfl(W.ord[k]);
+                const uint64_t bits = first64(W.key[i]);
+                const uint32_t mo = rfl(W.moff[i]), ml = rfl(W.mlen[i]);
+                s.kind = ml & INTF ? S_INT : S_RAW;
+                s.off = mo;
+                s.len = ml & ~INTF;
+                s.clen = 0;
+                s.iv = (int64_t)(int32_t)mo;
+                zl_push<EMIT>(r, s, z, zb, W.win);
+                int64_t iv;
+                const uint32_t cls = score_class(bits, iv);
+                if (cls == SC_INT) zl_push_int<EMIT>(z, zb, iv);
+                else {
+                    const uint32_t tl = cls == SC_INF ? 3u : cls == SC_NINF ? 4u : 2u;
+                    const uint64_t d = zl_str_hdr<EMIT>(z, zb, tl);
+                    if (EMIT && lane == 0) {
+                        uint8_t *t = zb + d;
+                        if (cls == SC_NZERO) { t[0] = '-'; t[1] = '0'; }
+                        else {
+                            if (cls == SC_NINF) *t++ = '-';
+                            t[0] = 'i'; t[1] = 'n'; t[2] = 'f';
+                        }
+                    }
+                    zl_advance(z, d + tl);
+                }
+            }
+            nel += cnt_in;
+            otype = RR_TYPE_ZSET_ZIPLIST;
+            wave_sync();
+        }
+        const uint64_t total = z.pos + 1;
+        if (total >= MAX_SLICE) { otype = 0; return 0; }
+        if (EMIT && lane == 0) {
+            put_le(out + 5, total, 8);
+            put_le(zb, total, 4);
+            put_le(zb + 4, z.last, 4);
+            put_le(zb + 8, entries, 2);
+            zb[z.pos] = 0xFF;
+        }
+        pay += total;
+        size = 13 + total;
+    }
+    if (EMIT && lane == 0) {
+        out[0] = (uint8_t)otype;
+        put_le(out + 1, O.lru, 4);
+    }
+    status = RR_OK;
+    return size;
+}
+
+// att[i] = 1 for the attempted values (att[n] = 0), everything a value that is not converted keeps
+// (RR_RDBCONVERT_SKIP or E_CONVERT, size 0, type 0), and the zeroing the other launches rely on (both
+// scans' look-back and error words, the totals)
+__global__ __launch_bounds__(256) void rdbconvert_flag_kernel(const uint8_t *__restrict__ load_status, uint64_t n,
+                                                              uint64_t *__restrict__ att, uint64_t *__restrict__ out_offs,
+                                                              uint8_t *__restrict__ out_types, uint8_t *__restrict__ status,
+                                                              uint64_t *__restrict__ zero, uint64_t nzero, rr_totals *totals) {
+    const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t gtid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint64_t k = gtid; k < nzero; k += nthreads) zero[k] = 0;
+    if (gtid == 0) {
+        att[n] = 0;
+        out_offs[n] = 0;
+        totals->n_elems = totals->bytes = totals->n_bad = totals->payload = 0;
+    }
+    for (uint64_t i = gtid; i < n; i += nthreads) {
+        const bool a = load_status[i] == RR_RDBLOAD_E_CONVERT;
+        att[i] = a ? 1 : 0;
+        out_offs[i] = 0;
+        out_types[i] = 0;
+        status[i] = a ? RR_RDBLOAD_E_CONVERT : RR_RDBCONVERT_SKIP;
+    }
+}
+
+// att scanned: list[att[i]] = i for the attempted values
+__global__ __launch_bounds__(256) void rdbconvert_compact_kernel(const uint8_t *__restrict__ load_status, uint64_t n,
+                                                                 const uint64_t *__restrict__ att, uint32_t *__restrict__ list) {
+    const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += nthreads)
+        if (load_status[i] == RR_RDBLOAD_E_CONVERT) list[att[i]] = (uint32_t)i;
+}
+
+// blob sizes into out_offs[], status and out_types of the list's values (att[n] of them)
+__global__ __launch_bounds__(WPB * RR_WAVE) void rdbconvert_size_kernel(const uint8_t *__restrict__ data, uint64_t in_cap,
+                                                                        const uint64_t *__restrict__ in_offs,
+                                                                        const uint8_t *__restrict__ types, uint64_t n,
+                                                                        const uint32_t *__restrict__ list,
+                                                                        const uint64_t *__restrict__ att, Opt O,
+                                                                        uint64_t *__restrict__ out_offs, uint8_t *__restrict__ out_types,
+                                                                        uint8_t *__restrict__ status) {
+    const Lds W = wave_lds();
+    const uint64_t gtid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t nwaves = (uint64_t)gridDim.x * blockDim.x / RR_WAVE;
+    const uint64_t m = first64(att[n]);
+    for (uint64_t k = first64(gtid / RR_WAVE); k < m; k += nwaves) {
+        const uint64_t v = rfl(list[k]);
+        const uint32_t type = rfl(types[v]);
+        const uint64_t o0 = first64(in_offs[v]), o1 = first64(in_offs[v + 1]);
+        uint32_t st = RR_RDBLOAD_E_CONVERT, ot = 0;
+        uint64_t size = 0, pay = 0, nel = 0;
+        if (o0 <= o1 && o1 <= in_cap && o1 - o0 < MAX_SLICE) {
+            Rd r = {mk_rsrc(data + o0, (uint32_t)(o1 - o0)), data + o0, (uint32_t)(o1 - o0), 0};
+            size = convert_value<false>(r, type, O, W, nullptr, st, ot, pay, nel);
+        }
+        if (lane_id() == 0 && st == RR_OK) {
+            out_offs[v] = size;
+            out_types[v] = (uint8_t)ot;
+            status[v] = RR_OK;
+        }
+    }
+}
+
+// out_offs scanned.  Writes the blobs of the converted values that fit out_cap; RR_E_CAPACITY for
+// those that do not; the totals.
+__global__ __launch_bounds__(WPB * RR_WAVE) void rdbconvert_emit_kernel(const uint8_t *__restrict__ data,
+                                                                        const uint64_t *__restrict__ in_offs,
+                                                                        const uint8_t *__restrict__ types, uint64_t n,
+                                                                        const uint32_t *__restrict__ list,
+                                                                        const uint64_t *__restrict__ att, Opt O,
+                                                                        const uint64_t *__restrict__ out_offs, uint8_t *out,
+                                                                        uint64_t out_cap, uint8_t *status, const uint64_t *err1,
+                                                                        const uint64_t *err2, rr_totals *totals) {
+    const Lds W = wave_lds();
+    const uint64_t gtid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t nwaves = (uint64_t)gridDim.x * blockDim.x / RR_WAVE;
+    if (gtid == 0) totals->bytes = (*err1 | *err2) ? ~0ull : out_offs[n];
+    const uint64_t m = first64(att[n]);
+    uint64_t pay = 0, nel = 0, n_bad = 0;   // wave-uniform
+    for (uint64_t k = first64(gtid / RR_WAVE); k < m; k += nwaves) {
+        const uint64_t v = rfl(list[k]);
+        uint32_t st = rfl(status[v]), ot;
+        if (st) { ++n_bad; continue; }
+        const uint64_t b0 = first64(out_offs[v]), b1 = first64(out_offs[v + 1]);
+        if (b1 > out_cap) {
+            ++n_bad;
+            if (lane_id() == 0) status[v] = RR_E_CAPACITY;
+            continue;
+        }
+        const uint32_t type = rfl(types[v]);
+        const uint64_t o0 = first64(in_offs[v]), o1 = first64(in_offs[v + 1]);
+        Rd r = {mk_rsrc(data + o0, (uint32_t)(o1 - o0)), data + o0, (uint32_t)(o1 - o0), 0};
+        convert_value<true>(r, type, O, W, out + b0, st, ot, pay, nel);
+    }
+    if (lane_id() == 0) {
+        if (pay) atomicAdd((unsigned long long *)&totals->payload, (unsigned long long)pay);
+        if (nel) atomicAdd((unsigned long long *)&totals->n_elems, (unsigned long long)nel);
+        if (n_bad) atomicAdd((unsigned long long *)&totals->n_bad, (unsigned long long)n_bad);
+    }
+}
+
+uint32_t wave_grid(uint64_t n) {   // a wave a value, capped
+    const uint64_t b = (n + WPB - 1) / WPB;
+    return (uint32_t)(b < GRID_CAP ? (b ? b : 1) : GRID_CAP);
+}
+uint32_t thread_grid(uint64_t n) {   // a thread a value, capped
+    const uint64_t b = (n + 255) / 256;
+    return (uint32_t)(b < 16384 ? (b ? b : 1) : 16384);
+}
+
+}  // namespace
+
+// scratch: two scans' look-back and error words, att[n + 1], list[n] (u32)
+extern "C" uint64_t rr_rdbconvert_scratch_words(uint64_t n) { return 2 * (rr_scan_words(n) + 1) + (n + 1) + (n + 1) / 2 + 1; }
+
+extern "C" hipError_t rr_launch_rdbconvert(const uint8_t *data, uint64_t in_cap, const uint64_t *in_offs, const uint8_t *types,
+                                           const uint8_t *load_status, uint64_t n, const uint32_t *opt6, uint8_t *out,
+                                           uint64_t out_cap, uint64_t *out_offs, uint8_t *out_types, uint8_t *status,
+                                           uint64_t *scratch, rr_totals *totals, hipStream_t stream) {
+    const uint64_t lbw = rr_scan_words(n);
+    uint64_t *lb1 = scratch, *err1 = lb1 + lbw, *lb2 = err1 + 1, *err2 = lb2 + lbw, *att = err2 + 1;
+    uint32_t *list = (uint32_t *)(att + n + 1);
+    const Opt O = {opt6[0], opt6[1], opt6[2], opt6[3], opt6[4], opt6[5]};
+    hipLaunchKernelGGL(rdbconvert_flag_kernel, dim3(thread_grid(n)), dim3(256), 0, stream, load_status, n, att, out_offs, out_types,
+                       status, scratch, 2 * (lbw + 1), totals);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = rr_launch_scan_u64(att, n, lb1, err1, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(rdbconvert_compact_kernel, dim3(thread_grid(n)), dim3(256), 0, stream, load_status, n, (const uint64_t *)att,
+                       list);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(rdbconvert_size_kernel, dim3(wave_grid(n)), dim3(WPB * RR_WAVE), 0, stream, data, in_cap, in_offs, types, n,
+                       (const uint32_t *)list, (const uint64_t *)att, O, out_offs, out_types, status);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = rr_launch_scan_u64(out_offs, n, lb2, err2, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(rdbconvert_emit_kernel, dim3(wave_grid(n)), dim3(WPB * RR_WAVE), 0, stream, data, in_offs, types, n,
+                       (const uint32_t *)list, (const uint64_t *)att, O, (const uint64_t *)out_offs, out, out_cap, status,
+                       (const uint64_t *)err1, (const uint64_t *)err2, totals);
+    return hipGetLastError();
+}

@@ -14,8 +14,9 @@ uint64_t rr_rdbload_bound(uint64_t n, uint64_t payload_bytes) {
     return (5 * n + 8 * payload_bytes + 15) & ~15ull;
 }
 
-/* lru, then the five thresholds: what the kernels take.  The defaults are config.c:2261-2267. */
-static int resolve_opts(const rr_rdbload_opts *o, uint32_t k[6]) {
+/* lru, then the five thresholds: what the kernels take.  The defaults are config.c:2261-2267.
+ * (rr_rdbconvert_api.c takes the same options through it.) */
+int rr_rdbload_resolve_opts(const rr_rdbload_opts *o, uint32_t k[6]) {
     static const rr_rdbload_opts def = {0, 512, 512, 64, 128, 64, 0};
     if (!o) o = &def;
     if (o->flags) return fail(RR_API_EINVAL, "rr_rdbload_opts.flags: unknown bit");
@@ -33,7 +34,7 @@ static int resolve_opts(const rr_rdbload_opts *o, uint32_t k[6]) {
 int rr_rdbload_batch(rr_ctx *c, const rr_blob_batch *in, const uint8_t *types, rr_blob_batch *out, uint8_t *status,
                      rr_totals *d_totals, const rr_rdbload_opts *opts, void *stream) {
     uint32_t k[6];
-    int rc = resolve_opts(opts, k);   /* first: the options are checked whatever else is wrong */
+    int rc = rr_rdbload_resolve_opts(opts, k);   /* first: the options are checked whatever else is wrong */
     if (rc) return rc;
     rc = rr_check_blob_io(c, in, out, d_totals, types && status);
     if (rc) return rc;
@@ -49,7 +50,7 @@ int rr_rdbload_batch_host(rr_ctx *c, const uint8_t *data, const uint64_t *offset
                           const rr_rdbload_opts *opts, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
                           uint8_t *status, rr_totals *totals) {
     uint32_t k[6];
-    int rc = resolve_opts(opts, k);
+    int rc = rr_rdbload_resolve_opts(opts, k);
     if (rc) return rc;
     if (!c || !offsets || !out_offsets || (n && (!types || !status)) || (out_cap && !out))
         return fail(RR_API_EINVAL, "NULL argument");

@@ -46,16 +46,6 @@ __device__ __forceinline__ uint64_t sum_lanes(uint64_t x) {
     return (uint64_t)rl32(a, RR_WAVE - 1) + ((uint64_t)rl32(b, RR_WAVE - 1) << 24) + ((uint64_t)rl32(c, RR_WAVE - 1) << 48);
 }
 
-// ---- ziplist entries (ziplist.c:332-364, :480-534) ----
-__device__ __forceinline__ uint32_t zint_bytes(int64_t v) {
-    return v >= 0 && v <= 12 ? 0u : v >= -128 && v <= 127 ? 1u : v >= -32768 && v <= 32767 ? 2u
-         : v >= -8388608 && v <= 8388607 ? 3u : is_i32(v) ? 4u : 8u;
-}
-__device__ __forceinline__ uint32_t zint_enc(int64_t v) {
-    const uint32_t nb = zint_bytes(v);
-    return nb == 0 ? 0xF1u + (uint32_t)v : nb == 1 ? 0xFEu : nb == 2 ? 0xC0u : nb == 3 ? 0xF0u : nb == 4 ? 0xD0u : 0xE0u;
-}
-__device__ __forceinline__ uint32_t zstr_hdr(uint32_t len) { return len <= 0x3F ? 1u : len <= 0x3FFF ? 2u : 5u; }
 // the size estimate _quicklistNodeAllowInsert adds for a pushed string of sz bytes (quicklist.c:425-441)
 __device__ __forceinline__ uint64_t ql_estimate(uint64_t sz) {
     return sz + (sz < 254 ? 1 : 5) + (sz < 64 ? 1 : sz < 16384 ? 2 : 5);
