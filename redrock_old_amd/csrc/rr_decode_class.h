@@ -25,12 +25,6 @@ namespace rr {
 // Sets and hashes are separate classes so a batch knows wave-uniformly which members are keys.
 constexpr uint32_t C_STR = 0, C_IS = 1, C_LIST = 2, C_HT = 3, C_SL = 4, C_ZL = 5, C_EXACT = 6, C_HH = 7, C_N = 8;
 
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-
-__device__ __forceinline__ rsrc_t make_rsrc(const uint8_t *base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)bytes, 0x00020000);
-}
-
 // bytes [p, p + 4N) of the tile (tile-relative p) into N dwords; reads past the descriptor's
 // range give zero bytes
 template <int N>

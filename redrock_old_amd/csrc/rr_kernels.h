@@ -1,5 +1,5 @@
-/* rr_kernels.h — launch entry points of rr_kernels.hip and rr_util.hip, called by the C host
- * layer (rr_api.c). */
+/* rr_kernels.h — the launch header of every kernel unit: the entry points the C host layer
+ * (rr_api.c and the *_api.c files) calls, grouped by the .hip file that defines them. */
 #ifndef RR_KERNELS_H
 #define RR_KERNELS_H
 
@@ -18,6 +18,7 @@
 extern "C" {
 #endif
 
+/* rr_kernels.hip, the decode (include/rr_serdes.h) */
 /* sums: rr_decode_sums_words(data_cap) words, zero on entry (count_kernel adds the window and
  * group sums into them, decode_kernel reads them; a batch of one window generation runs
  * decode_kernel's one-launch form alone, which keeps its look-back and end words there and leaves
@@ -30,14 +31,39 @@ hipError_t rr_launch_decode(const uint8_t *blob, const uint64_t *offsets, uint64
                             uint64_t *zero, uint64_t nzero, uint64_t data_cap, rr_totals *totals, hipStream_t stream,
                             int first_only, unsigned flags);
 uint64_t rr_decode_sums_words(uint64_t data_cap);
-hipError_t rr_launch_zero_words(uint64_t *words, uint64_t n, hipStream_t stream);
+uint64_t rr_decode_scratch_words(uint64_t data_cap, uint64_t n);
+/* small batches (one workgroup, one launch; the encode's likewise): whether a batch qualifies, and
+ * the launch; a non-NULL done (host-mapped) receives seq once every result is visible to the host */
+int rr_small_decode_fits(uint64_t n, uint64_t data_cap);
+hipError_t rr_launch_decode_small(const uint8_t *blob, const uint64_t *offsets, uint64_t n, rr_value *values,
+                                  rr_elem *elems, uint64_t elem_cap, uint8_t *arena, uint64_t data_cap, rr_totals *totals,
+                                  uint32_t *done, uint32_t seq, unsigned flags, hipStream_t stream);
+/* rr_kernels.hip, the encode (include/rr_serdes.h) */
 hipError_t rr_launch_encode(const rr_value *values, const rr_elem *elems, uint64_t elem_cap, const uint8_t *arena,
                             uint64_t arena_cap, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *offsets,
                             uint64_t *scratch, uint64_t *sums, rr_totals *totals, hipStream_t stream, int first_only);
 uint64_t rr_encode_sums_words(uint64_t n);
-uint64_t rr_decode_scratch_words(uint64_t data_cap, uint64_t n);
+uint64_t rr_encode_scratch_words(uint64_t n, uint64_t data_cap);
+int rr_small_encode_fits(uint64_t n, uint64_t data_cap);
+hipError_t rr_launch_encode_small(const rr_value *values, const rr_elem *elems, uint64_t elem_cap, const uint8_t *arena,
+                                  uint64_t arena_cap, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *offsets,
+                                  rr_totals *totals, uint32_t *done, uint32_t seq, hipStream_t stream);
+/* the pipelined host encode: the end of the arena bytes the valid values [0, n) read, as
+ * RR_NEED_BLOCKS partial maxima into mapped host words */
+#define RR_NEED_BLOCKS 32
+hipError_t rr_launch_arena_need(const rr_value *values, uint64_t n, const rr_elem *elems, uint64_t elem_cap,
+                                uint64_t arena_cap, uint64_t *need, hipStream_t stream);
+/* rr_util.hip: zeroing, the look-back scan, the shard helpers of rr_shard.c, the copy kernel */
+hipError_t rr_launch_zero_words(uint64_t *words, uint64_t n, hipStream_t stream);
 uint64_t rr_scan_words(uint64_t n);
 hipError_t rr_launch_scan_u64(uint64_t *x, uint64_t n, uint64_t *lb, uint64_t *err, hipStream_t stream);
+hipError_t rr_launch_shard_plan(const uint64_t *offsets, uint64_t n, uint32_t g, uint64_t *plan, hipStream_t stream);
+hipError_t rr_launch_offsets_rebase(uint64_t *offs, uint64_t count, uint64_t sub, hipStream_t stream);
+hipError_t rr_launch_flat_rebase(rr_value *values, uint64_t n, rr_elem *elems, uint64_t ne, uint64_t elem_add,
+                                 uint64_t byte_add, hipStream_t stream);
+hipError_t rr_launch_copy(uint8_t *dst, const uint8_t *src, uint64_t bytes, hipStream_t stream);
+hipError_t rr_launch_copy_shape(uint8_t *dst, const uint8_t *src, uint64_t bytes, int shape, hipStream_t stream);
+/* rr_snappy.hip (include/rr_snappy.h) */
 uint64_t rr_snappy_scratch_words(uint64_t n, uint64_t slot_bytes);
 hipError_t rr_launch_snappy_decompress(const uint8_t *in, uint64_t in_cap, const uint64_t *in_offs, uint64_t n, uint8_t *out,
                                        uint64_t out_cap, uint64_t *out_offs, uint8_t *status, uint64_t *scratch,
@@ -98,28 +124,6 @@ hipError_t rr_launch_rdbdump(const uint8_t *data, uint64_t in_cap, const uint64_
 hipError_t rr_launch_rdbdump_verify(const uint8_t *data, uint64_t in_cap, const uint64_t *in_offs, uint64_t n, uint8_t *out,
                                     uint64_t out_cap, uint64_t *out_offs, uint8_t *types, uint8_t *status, uint64_t *scratch,
                                     struct rr_rdbfile_result *result, hipStream_t stream);
-hipError_t rr_launch_shard_plan(const uint64_t *offsets, uint64_t n, uint32_t g, uint64_t *plan, hipStream_t stream);
-hipError_t rr_launch_offsets_rebase(uint64_t *offs, uint64_t count, uint64_t sub, hipStream_t stream);
-hipError_t rr_launch_flat_rebase(rr_value *values, uint64_t n, rr_elem *elems, uint64_t ne, uint64_t elem_add,
-                                 uint64_t byte_add, hipStream_t stream);
-uint64_t rr_encode_scratch_words(uint64_t n, uint64_t data_cap);
-hipError_t rr_launch_copy(uint8_t *dst, const uint8_t *src, uint64_t bytes, hipStream_t stream);
-hipError_t rr_launch_copy_shape(uint8_t *dst, const uint8_t *src, uint64_t bytes, int shape, hipStream_t stream);
-/* the pipelined host encode: the end of the arena bytes the valid values [0, n) read, as
- * RR_NEED_BLOCKS partial maxima into mapped host words */
-#define RR_NEED_BLOCKS 32
-hipError_t rr_launch_arena_need(const rr_value *values, uint64_t n, const rr_elem *elems, uint64_t elem_cap,
-                                uint64_t arena_cap, uint64_t *need, hipStream_t stream);
-/* small batches (one workgroup, one launch): whether a batch qualifies, and the launches; a
- * non-NULL done (host-mapped) receives seq once every result is visible to the host */
-int rr_small_decode_fits(uint64_t n, uint64_t data_cap);
-int rr_small_encode_fits(uint64_t n, uint64_t data_cap);
-hipError_t rr_launch_decode_small(const uint8_t *blob, const uint64_t *offsets, uint64_t n, rr_value *values,
-                                  rr_elem *elems, uint64_t elem_cap, uint8_t *arena, uint64_t data_cap, rr_totals *totals,
-                                  uint32_t *done, uint32_t seq, unsigned flags, hipStream_t stream);
-hipError_t rr_launch_encode_small(const rr_value *values, const rr_elem *elems, uint64_t elem_cap, const uint8_t *arena,
-                                  uint64_t arena_cap, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *offsets,
-                                  rr_totals *totals, uint32_t *done, uint32_t seq, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,8 @@
 //   bytes in LDS (element-parallel tasks, aligned stores) and stores it coalesced.  Details at
 //   E1-E4.
 // Small batches (<= 4096 values, <= 128 KiB): one workgroup, one launch each way.
+// The file is two halves that share no code: the decode with its launch code, then the encode
+// with its launch code, each in an anonymous namespace of its own.
 // (What decode and encode share is in rr_flat_device.h; the shard helpers, the copy kernel and the
 // look-back scan are in rr_util.hip.)
 //
@@ -1210,7 +1212,7 @@ __global__ __launch_bounds__(NW * RR_WAVE) __attribute__((amdgpu_waves_per_eu(DE
         const uint64_t LE = W0 + win < data_cap ? W0 + win : data_cap;
         ov_a = W0 >> 4;
         ov_mb = LE > W0 ? (uint32_t)(LE - W0) : 0u;
-        ov_RM = make_rsrc(blob + W0, ov_mb);
+        ov_RM = mk_rsrc(blob + W0, ov_mb);
         const uint64_t on = offsets[n];
         uint64_t vv[2], ff[2];
         one_locate<NT>(offsets, n, win, data_cap, tile, on, reinterpret_cast<uint64_t *>(stage), &wpart[0][0], vv, ff,
@@ -1243,7 +1245,7 @@ __global__ __launch_bounds__(NW * RR_WAVE) __attribute__((amdgpu_waves_per_eu(DE
         // offset 16 (tid + k NT)
         ov_a = A0 >> 4;
         ov_mb = (W1 >> 4) > ov_a ? (uint32_t)(((W1 >> 4) - ov_a) * 16) : 0u;
-        ov_RM = make_rsrc(blob + A0, ov_mb);
+        ov_RM = mk_rsrc(blob + A0, ov_mb);
         // KE granules per thread go out before the first_val -> offsets / class-byte loads, the
         // rest after the class bytes: the sort waits (vmcnt, in issue order) for the class bytes
         // and therefore for the early granules only
@@ -1265,7 +1267,7 @@ __global__ __launch_bounds__(NW * RR_WAVE) __attribute__((amdgpu_waves_per_eu(DE
     const uint64_t ov_w1 = W1 >> 4;
     // the arena gets [A0, W1): in the ONE form the loads start at W0, so granules below A0 (the
     // call's first value, in window 0 or in a slice of a larger buffer) are dropped
-    const rsrc_t ov_RA = make_rsrc(arena + ov_a * 16, ov_w1 > ov_a ? (uint32_t)((ov_w1 - ov_a) * 16) : 0u);
+    const rsrc_t ov_RA = mk_rsrc(arena + ov_a * 16, ov_w1 > ov_a ? (uint32_t)((ov_w1 - ov_a) * 16) : 0u);
     uint64_t S0 = W0, S1 = W0;
     if (v_hi > v_lo) {
         S0 = f_lo & ~15ull;
@@ -1305,7 +1307,7 @@ __global__ __launch_bounds__(NW * RR_WAVE) __attribute__((amdgpu_waves_per_eu(DE
     }
     // the stage's tail, also in flight under the sort
     const uint64_t ov_te = (staged && S1 > W1 ? S1 : W1) >> 4;
-    const rsrc_t ov_RT = make_rsrc(blob + ov_t0 * 16, ov_te > ov_t0 ? (uint32_t)((ov_te - ov_t0) * 16) : 0u);
+    const rsrc_t ov_RT = mk_rsrc(blob + ov_t0 * 16, ov_te > ov_t0 ? (uint32_t)((ov_te - ov_t0) * 16) : 0u);
     u32x4 ov_t[KT];
 #pragma unroll
     for (uint32_t k = 0; k < KT; ++k)
@@ -1352,7 +1354,7 @@ __global__ __launch_bounds__(NW * RR_WAVE) __attribute__((amdgpu_waves_per_eu(DE
     // bytes each; a staged window never comes near)
     const bool far = (!staged && S1 - S0 > 0xFFFFFF00ull) || ((S1 - S0) / 2 + (v_hi - v_lo)) * 16 >= NOSLOT;
     const LdsSrc lsrc{(lds_cptr)stage};
-    const GlbSrc gsrc{make_rsrc(blob + S0, (uint32_t)(data_cap - S0 < 0xFFFFFFFFull ? data_cap - S0 : 0xFFFFFFFFull))};
+    const GlbSrc gsrc{mk_rsrc(blob + S0, (uint32_t)(data_cap - S0 < 0xFFFFFFFFull ? data_cap - S0 : 0xFFFFFFFFull))};
     // ONE: a value's reservation and class (count_kernel's rule: reserve_classify, a List's
     // length chain) from the stage once it has landed, or from global memory for a window that
     // is not staged
@@ -1541,8 +1543,7 @@ __global__ __launch_bounds__(NW * RR_WAVE) __attribute__((amdgpu_waves_per_eu(DE
         lds_barrier();   // the stage and the chunk's sort are complete
         // the chunk's descriptor slots [eb_c, eb_c + ctot), cut at the capacity
         const uint64_t eb_c = eb0 + run, ecut = eb_c + ctot < cap ? eb_c + ctot : cap;
-        const rsrc_t E = make_rsrc(reinterpret_cast<const uint8_t *>(elems + eb_c),
-                                   far || ecut <= eb_c ? 0u : (uint32_t)((ecut - eb_c) * 16));
+        const rsrc_t E = mk_rsrc(elems + eb_c, far || ecut <= eb_c ? 0u : (uint32_t)((ecut - eb_c) * 16));
 
         PROBE(if (c0 == v_lo) pt2 = __builtin_amdgcn_s_memtime();)
         // 3. single-class batches, taken dynamically by the waves
@@ -1697,7 +1698,6 @@ __global__ __launch_bounds__(NW * RR_WAVE) __attribute__((amdgpu_waves_per_eu(DE
 // from LDS (the reference's statuses; the walks' results are the parser's by construction), the
 // fixup of marked values, and the totals — the same records, descriptors, arena and totals as
 // the pipeline, byte for byte.
-constexpr uint32_t SMALL_EIN = 16 * 1024;   // encode inputs up to this size staged in LDS
 constexpr uint32_t SMALL_STAGE = SMALL_BYTES + 8192;   // + the reads past a value's end; >= the fixup's LDS
 static_assert(FIX_LDS + 4 * (SMALL_NT + 1) <= SMALL_STAGE, "the fixup reuses the stage");
 
@@ -1794,8 +1794,7 @@ __global__ __launch_bounds__(SMALL_NT) void decode_small_kernel(const uint8_t *_
                 const bool grouped = c == C_LIST || c == C_SL || c == C_IS || c == C_ZL;
                 const bool htg = (c == C_HT || c == C_HH) && GMAX >= ht_group_min(c == C_HH);
                 const uint32_t G = grouped || htg ? GMAX : 1u;
-                const rsrc_t E = make_rsrc(reinterpret_cast<const uint8_t *>(elems + ev),
-                                           ev < cap ? (uint32_t)((cap - ev < rv ? cap - ev : rv) * 16) : 0u);
+                const rsrc_t E = mk_rsrc(elems + ev, ev < cap ? (uint32_t)((cap - ev < rv ? cap - ev : rv) * 16) : 0u);
                 a = run_batch(lsrc, c, lane < G, v, G, lane & (G - 1), B0, E, ev, blob, s_off, ev, rv, values, elems, cap,
                               &nfix, zraw);
             }
@@ -1834,6 +1833,169 @@ __global__ __launch_bounds__(SMALL_NT) void decode_small_kernel(const uint8_t *_
     }
     signal_done(done, seq);
 }
+
+}  // namespace
+
+extern "C" int rr_small_decode_fits(uint64_t n, uint64_t data_cap) {
+    return n <= SMALL_N && data_cap <= SMALL_BYTES && (n <= SMALL_GW || data_cap <= n * SMALL_LANE_BYTES);
+}
+extern "C" hipError_t rr_launch_decode_small(const uint8_t *blob, const uint64_t *offsets, uint64_t n, rr_value *values,
+                                             rr_elem *elems, uint64_t elem_cap, uint8_t *arena, uint64_t data_cap,
+                                             rr_totals *totals, uint32_t *done, uint32_t seq, unsigned flags,
+                                             hipStream_t stream) {
+    hipLaunchKernelGGL(decode_small_kernel, dim3(1), dim3(SMALL_NT), 0, stream, blob, offsets, n, values, elems, elem_cap,
+                       arena, data_cap, totals, done, seq, (uint32_t)(flags & RR_CTX_ZL_RAW));
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------- launch
+#ifndef RR_DEC_W
+#define RR_DEC_W 73728
+#endif
+#ifndef RR_DEC_SLACK
+#define RR_DEC_SLACK 4096
+#endif
+#ifndef RR_DEC_NW
+#define RR_DEC_NW 8
+#endif
+constexpr uint32_t DEC_W = RR_DEC_W, DEC_NW = RR_DEC_NW;
+// (values per sort chunk: one per thread, the chunk's slot scan)
+#define DECODE_KERNEL decode_kernel<RR_DEC_W, RR_DEC_SLACK, RR_DEC_NW, RR_DEC_NW * RR_WAVE>
+#define DECODE_ONE decode_kernel<RR_DEC_W, RR_DEC_SLACK, RR_DEC_NW, RR_DEC_NW * RR_WAVE, true>
+// (RR_DEC_ONE=0 in the environment: the two-launch form for every batch — A/B runs only)
+static bool dec_one(void) {
+    static int v = -1;
+    if (v < 0) {
+        const char *e = getenv("RR_DEC_ONE");
+        v = !(e && e[0] == '0');
+    }
+    return v != 0;
+}
+
+// Resident workgroup count of a kernel, as the occupancy query gives it (a persistent launch would
+// take one block per CU off: the API over-reports by one for SGPR-heavy kernels,
+// MI355X_MICROARCH.md §Residency).
+template <typename K>
+static uint32_t resident_grid(K kernel, int block) {
+    int dev = 0, cus = 0, occ = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, block, 0) != hipSuccess || occ < 1) occ = 1;
+    if (cus < 1) cus = 1;
+    return (uint32_t)(cus * occ);
+}
+
+// windows: sized from data_cap (>= offsets[n], host-known without a sync); windows past
+// offsets[n] own no values and copy nothing
+// The window size of a call: the batch cut into whole generations of the resident windows (two
+// per CU), each window as close to DEC_W as that allows — so the last generation is not a
+// partial one that leaves most CUs idle (config 4 at 1M values: 14 generations of 69.4 KiB
+// windows instead of 13.2 of 72 KiB), and a small batch spreads over every CU instead of a
+// few full windows (config 1 at 100K values: 512 windows of 13.7 KiB instead of 98).
+constexpr uint64_t DEC_WMIN = 1024;
+// Per-device launch facts (ADVICE r5): the calling thread's current device, which every entry
+// point of rr_api.c sets to its context's device first; one slot per device id, filled by
+// whichever thread gets there first (racing threads store the same value)
+constexpr int RR_MAX_DEV = 64;
+static uint32_t dev_cache(uint32_t (&cache)[RR_MAX_DEV], uint32_t (*query)(void)) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    uint32_t *slot = &cache[(uint32_t)dev % RR_MAX_DEV];
+    uint32_t v = __atomic_load_n(slot, __ATOMIC_RELAXED);
+    if (!v) {
+        v = query();
+        __atomic_store_n(slot, v, __ATOMIC_RELAXED);
+    }
+    return v;
+}
+static uint32_t q_dec_slots(void) { return resident_grid(DECODE_KERNEL, DEC_NW * RR_WAVE); }
+static uint32_t q_cus(void) {
+    int dev = 0, c = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
+    return c > 0 ? (uint32_t)c : 1u;
+}
+static uint32_t g_dec_slots[RR_MAX_DEV], g_cus[RR_MAX_DEV];
+static uint32_t dec_slots(void) { return dev_cache(g_dec_slots, q_dec_slots); }
+static uint32_t dev_cus(void) { return dev_cache(g_cus, q_cus); }
+static uint32_t dec_win(uint64_t data_cap) {
+    const uint64_t slots = dec_slots();
+    const uint64_t per_gen = slots * DEC_W, gens = (data_cap + per_gen - 1) / per_gen;
+    uint64_t w = gens ? (data_cap + gens * slots - 1) / (gens * slots) : DEC_WMIN;
+    w = (w + 15) & ~15ull;
+    return (uint32_t)(w < DEC_WMIN ? DEC_WMIN : w > DEC_W ? DEC_W : w);
+}
+static uint64_t dec_windows(uint64_t data_cap) { return data_cap / dec_win(data_cap) + 1; }
+
+// Decode scratch (uint64 words): [HDR] [reservations u32, n] [first_val u32, nwin + 1]
+// [first_off, nwin + 1] [class bytes, n].  The window and group sums are in a buffer of their
+// own (rr_decode_sums_words), zero between calls; count_kernel's block 0 zeroes the totals.
+// Launches: count_kernel, decode_kernel.  (Round 3 ran a look-back scan of the
+// reservations between the two — 15.4 us on config 4 — and a fourth kernel for the fixup and
+// the totals fold — 5.6 us.  Measured dead ends, in git history: a fused single-pass decode
+// with a window-level look-back, 0.401 vs 0.353 ms — the look-back waits ~5 us per window
+// generation; count + scan in one launch with an in-kernel look-back, +40 us.)
+static uint64_t dec_groups(uint64_t nw) { return nw / WGROUP + 1; }
+extern "C" uint64_t rr_decode_scratch_words(uint64_t data_cap, uint64_t n) {
+    const uint64_t nw = dec_windows(data_cap);
+    return RR_SCRATCH_HDR + (n + 2) / 2 + (nw + 2) / 2 + (nw + 1) + (n + 7) / 8 + 2;
+}
+// The sums (one half of the context's double buffer): [window sums, nwin] [group sums, nwin / WGROUP + 1],
+// or the one-launch form's words (one_words(nwin) <= this)
+extern "C" uint64_t rr_decode_sums_words(uint64_t data_cap) {
+    const uint64_t nw = dec_windows(data_cap), two = nw + dec_groups(nw);
+    return two > one_words(nw) ? two : one_words(nw);
+}
+
+extern "C" hipError_t rr_launch_decode(const uint8_t *blob, const uint64_t *offsets, uint64_t n, rr_value *values,
+                                       rr_elem *elems, uint64_t elem_cap, uint8_t *arena, uint64_t *scratch,
+                                       uint64_t *sums, uint64_t *zero, uint64_t nzero, uint64_t data_cap,
+                                       rr_totals *totals, hipStream_t stream, int first_only, unsigned flags) {
+    const uint32_t zraw = flags & RR_CTX_ZL_RAW ? DEC_ZL_RAW : 0u;
+    uint32_t win = dec_win(data_cap), nw = (uint32_t)(data_cap / win + 1);
+    // A small batch that fits one window per CU, at most a sort chunk (512 values) a window, gets
+    // one window per CU instead of two: config 1 at 100K values 22.0 -> 19.1 us, config 2 / 4 at
+    // 30K values -16 % / -10 %; at 200K config-1 values (781 a window) two per CU stay faster
+    // (profiles/r5_small_windows_ab.txt).  Fewer windows than dec_windows(data_cap): the scratch
+    // and the sums sized from data_cap still cover them.
+    const uint64_t cus = dev_cus();
+    if (data_cap <= cus * DEC_W && n <= cus * DEC_NW * RR_WAVE) {
+        uint64_t w = ((data_cap + cus - 1) / cus + 15) & ~15ull;
+        w = w < DEC_WMIN ? DEC_WMIN : w;
+        if (w > win) {
+            win = (uint32_t)w;
+            nw = (uint32_t)(data_cap / win + 1);
+        }
+    }
+    // A batch of one generation of windows: one launch (decode_kernel's ONE form) instead of
+    // count_kernel + decode_kernel.  (The debug hook that withholds the second launch keeps the
+    // two-launch form, which it tests.)
+    uint64_t *wtot = sums;
+    uint64_t *gtot = wtot + nw;
+    uint32_t *counts = reinterpret_cast<uint32_t *>(scratch + RR_SCRATCH_HDR);
+    uint32_t *first_val = counts + ((n + 2) & ~1ull);
+    uint64_t *first_off = reinterpret_cast<uint64_t *>(first_val + ((nw + 2) & ~1u));
+    uint8_t *cls = reinterpret_cast<uint8_t *>(first_off + nw + 1);
+    if (first_only != 1 && nw <= dec_slots() && nw <= DEC_NW * RR_WAVE && dec_one()) {   // (a look-back thread per earlier window)
+        hipLaunchKernelGGL((DECODE_ONE), dim3(nw), dim3(DEC_NW * RR_WAVE), 0, stream, blob, data_cap, offsets, n,
+                           nullptr, nullptr, cls, counts, nullptr, nullptr, values, elems, elem_cap, arena, nw, win,
+                           totals, sums, zero, nzero, (first_only == 2 ? DEC_HELP_ALL : 0u) | zraw);
+        return hipGetLastError();
+    }
+    if (data_cap < (1ull << 32))
+        hipLaunchKernelGGL(count_kernel<true>, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, stream, blob, offsets, n,
+                           first_val, first_off, nw, win, counts, cls, wtot, gtot, zero, nzero, totals, zraw);
+    else
+        hipLaunchKernelGGL(count_kernel<false>, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, stream, blob, offsets,
+                           n, first_val, first_off, nw, win, counts, cls, wtot, gtot, zero, nzero, totals, zraw);
+    if (first_only == 1) return hipGetLastError();
+    hipLaunchKernelGGL((DECODE_KERNEL), dim3(nw), dim3(DEC_NW * RR_WAVE), 0, stream, blob, data_cap, offsets, n,
+                       first_val, first_off, cls, counts, wtot, gtot, values, elems, elem_cap, arena, nw, win, totals,
+                       nullptr, nullptr, 0, zraw);
+    return hipGetLastError();
+}
+
+namespace {
 
 // ---------------------------------------------------------------------------------------- encode
 // The encode's totals: E1's and E3's per-tile partials {bad, payload, descriptors} (3 words a
@@ -2579,8 +2741,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ENC_WPE))) v
     // (encode config 4 -1.5 %, config 2 -5 %, profiles/r5_encode_persistent_ab.txt "p0")
     auto first_round = [&](uint64_t v0, uint64_t vend, uint64_t &a, uint64_t &b, uint4 &x) {
         const uint32_t nv = vend - v0 < NT ? (uint32_t)(vend - v0) : NT;
-        const rsrc_t RO = make_rsrc(reinterpret_cast<const uint8_t *>(offsets + v0), (nv + 1) * 8u);
-        const rsrc_t RV = make_rsrc(reinterpret_cast<const uint8_t *>(values + v0), nv * 16u);
+        const rsrc_t RO = mk_rsrc(offsets + v0, (nv + 1) * 8u);
+        const rsrc_t RV = mk_rsrc(values + v0, nv * 16u);
         const uint32_t t = threadIdx.x;
         a = __builtin_bit_cast(uint64_t, __builtin_amdgcn_raw_buffer_load_b64(RO, (int)(t * 8), 0, 0));
         b = __builtin_bit_cast(uint64_t, __builtin_amdgcn_raw_buffer_load_b64(RO, (int)(t * 8 + 8), 0, 0));
@@ -2859,13 +3021,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(ENC_WPE))) v
     // store the image: 16-byte chunks (buffer stores: chunks past the window's span are dropped,
     // every thread issues the same W / 16 / NT stores), then the bytes of a partial last chunk
     {
-        const rsrc_t RS = make_rsrc(out + w0, (uint32_t)span & ~15u);
+        const rsrc_t RS = mk_rsrc(out + w0, (uint32_t)span & ~15u);
         const u32x4 *src4 = reinterpret_cast<const u32x4 *>(img4);
 #pragma unroll
         for (uint32_t k = 0; k < W / 16 / NT; ++k)
             __builtin_amdgcn_raw_buffer_store_b128(src4[tid + k * NT], RS, (int)((tid + k * NT) * 16), 0, 2 /* nt */);
         const uint32_t full = (uint32_t)(span >> 4), tail = (uint32_t)(span & 15);
-        const rsrc_t RT = make_rsrc(out + w0 + 16ull * full, tail);
+        const rsrc_t RT = mk_rsrc(out + w0 + 16ull * full, tail);
         __builtin_amdgcn_raw_buffer_store_b8(img[(16u * full + (tid & 15u)) & (W - 1)], RT, (int)tid, 0, 0);
     }
     EPROBE(const uint64_t et4 = rr_stamp();
@@ -3033,6 +3195,8 @@ __device__ void emit_value_wave(uint8_t *img, uint64_t p, const uint4 &x, const 
     }
 }
 
+constexpr uint32_t SMALL_EIN = 16 * 1024;   // encode inputs up to this size staged in LDS
+
 __global__ __launch_bounds__(SMALL_NT) void encode_small_kernel(const rr_value *__restrict__ values,
                                                                 const rr_elem *__restrict__ elems, uint64_t ecap,
                                                                 const uint8_t *__restrict__ arena, uint64_t acap,
@@ -3163,18 +3327,6 @@ __global__ __launch_bounds__(SMALL_NT) void encode_small_kernel(const rr_value *
 
 }  // namespace
 
-extern "C" int rr_small_decode_fits(uint64_t n, uint64_t data_cap) {
-    return n <= SMALL_N && data_cap <= SMALL_BYTES && (n <= SMALL_GW || data_cap <= n * SMALL_LANE_BYTES);
-}
-extern "C" hipError_t rr_launch_decode_small(const uint8_t *blob, const uint64_t *offsets, uint64_t n, rr_value *values,
-                                             rr_elem *elems, uint64_t elem_cap, uint8_t *arena, uint64_t data_cap,
-                                             rr_totals *totals, uint32_t *done, uint32_t seq, unsigned flags,
-                                             hipStream_t stream) {
-    hipLaunchKernelGGL(decode_small_kernel, dim3(1), dim3(SMALL_NT), 0, stream, blob, offsets, n, values, elems, elem_cap,
-                       arena, data_cap, totals, done, seq, (uint32_t)(flags & RR_CTX_ZL_RAW));
-    return hipGetLastError();
-}
-
 // ---- the pipelined host encode: which arena bytes a chunk of values reads ----------------
 // The largest end (data + len) of the STR / ZLRAW descriptors of the values the encode will read
 // (status RR_OK, descriptors inside elem_cap: encode_size's conditions), clamped to arena_cap:
@@ -3229,152 +3381,6 @@ extern "C" hipError_t rr_launch_encode_small(const rr_value *values, const rr_el
 }
 
 // ---------------------------------------------------------------------------------------- launch
-#ifndef RR_DEC_W
-#define RR_DEC_W 73728
-#endif
-#ifndef RR_DEC_SLACK
-#define RR_DEC_SLACK 4096
-#endif
-#ifndef RR_DEC_NW
-#define RR_DEC_NW 8
-#endif
-constexpr uint32_t DEC_W = RR_DEC_W, DEC_NW = RR_DEC_NW;
-// (values per sort chunk: one per thread, the chunk's slot scan)
-#define DECODE_KERNEL decode_kernel<RR_DEC_W, RR_DEC_SLACK, RR_DEC_NW, RR_DEC_NW * RR_WAVE>
-#define DECODE_ONE decode_kernel<RR_DEC_W, RR_DEC_SLACK, RR_DEC_NW, RR_DEC_NW * RR_WAVE, true>
-// (RR_DEC_ONE=0 in the environment: the two-launch form for every batch — A/B runs only)
-static bool dec_one(void) {
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("RR_DEC_ONE");
-        v = !(e && e[0] == '0');
-    }
-    return v != 0;
-}
-
-// Resident workgroup count of a kernel, as the occupancy query gives it (a persistent launch would
-// take one block per CU off: the API over-reports by one for SGPR-heavy kernels,
-// MI355X_MICROARCH.md §Residency).
-template <typename K>
-static uint32_t resident_grid(K kernel, int block) {
-    int dev = 0, cus = 0, occ = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, block, 0) != hipSuccess || occ < 1) occ = 1;
-    if (cus < 1) cus = 1;
-    return (uint32_t)(cus * occ);
-}
-
-// windows: sized from data_cap (>= offsets[n], host-known without a sync); windows past
-// offsets[n] own no values and copy nothing
-// The window size of a call: the batch cut into whole generations of the resident windows (two
-// per CU), each window as close to DEC_W as that allows — so the last generation is not a
-// partial one that leaves most CUs idle (config 4 at 1M values: 14 generations of 69.4 KiB
-// windows instead of 13.2 of 72 KiB), and a small batch spreads over every CU instead of a
-// few full windows (config 1 at 100K values: 512 windows of 13.7 KiB instead of 98).
-constexpr uint64_t DEC_WMIN = 1024;
-// Per-device launch facts (ADVICE r5): the calling thread's current device, which every entry
-// point of rr_api.c sets to its context's device first; one slot per device id, filled by
-// whichever thread gets there first (racing threads store the same value)
-constexpr int RR_MAX_DEV = 64;
-static uint32_t dev_cache(uint32_t (&cache)[RR_MAX_DEV], uint32_t (*query)(void)) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    uint32_t *slot = &cache[(uint32_t)dev % RR_MAX_DEV];
-    uint32_t v = __atomic_load_n(slot, __ATOMIC_RELAXED);
-    if (!v) {
-        v = query();
-        __atomic_store_n(slot, v, __ATOMIC_RELAXED);
-    }
-    return v;
-}
-static uint32_t q_dec_slots(void) { return resident_grid(DECODE_KERNEL, DEC_NW * RR_WAVE); }
-static uint32_t q_cus(void) {
-    int dev = 0, c = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-    return c > 0 ? (uint32_t)c : 1u;
-}
-static uint32_t g_dec_slots[RR_MAX_DEV], g_cus[RR_MAX_DEV];
-static uint32_t dec_slots(void) { return dev_cache(g_dec_slots, q_dec_slots); }
-static uint32_t dev_cus(void) { return dev_cache(g_cus, q_cus); }
-static uint32_t dec_win(uint64_t data_cap) {
-    const uint64_t slots = dec_slots();
-    const uint64_t per_gen = slots * DEC_W, gens = (data_cap + per_gen - 1) / per_gen;
-    uint64_t w = gens ? (data_cap + gens * slots - 1) / (gens * slots) : DEC_WMIN;
-    w = (w + 15) & ~15ull;
-    return (uint32_t)(w < DEC_WMIN ? DEC_WMIN : w > DEC_W ? DEC_W : w);
-}
-static uint64_t dec_windows(uint64_t data_cap) { return data_cap / dec_win(data_cap) + 1; }
-
-// Decode scratch (uint64 words): [HDR] [reservations u32, n] [first_val u32, nwin + 1]
-// [first_off, nwin + 1] [class bytes, n].  The window and group sums are in a buffer of their
-// own (rr_decode_sums_words), zero between calls; count_kernel's block 0 zeroes the totals.
-// Launches: count_kernel, decode_kernel.  (Round 3 ran a look-back scan of the
-// reservations between the two — 15.4 us on config 4 — and a fourth kernel for the fixup and
-// the totals fold — 5.6 us.  Measured dead ends, in git history: a fused single-pass decode
-// with a window-level look-back, 0.401 vs 0.353 ms — the look-back waits ~5 us per window
-// generation; count + scan in one launch with an in-kernel look-back, +40 us.)
-static uint64_t dec_groups(uint64_t nw) { return nw / WGROUP + 1; }
-extern "C" uint64_t rr_decode_scratch_words(uint64_t data_cap, uint64_t n) {
-    const uint64_t nw = dec_windows(data_cap);
-    return RR_SCRATCH_HDR + (n + 2) / 2 + (nw + 2) / 2 + (nw + 1) + (n + 7) / 8 + 2;
-}
-// The sums (one half of the context's double buffer): [window sums, nwin] [group sums, nwin / WGROUP + 1],
-// or the one-launch form's words (one_words(nwin) <= this)
-extern "C" uint64_t rr_decode_sums_words(uint64_t data_cap) {
-    const uint64_t nw = dec_windows(data_cap), two = nw + dec_groups(nw);
-    return two > one_words(nw) ? two : one_words(nw);
-}
-
-extern "C" hipError_t rr_launch_decode(const uint8_t *blob, const uint64_t *offsets, uint64_t n, rr_value *values,
-                                       rr_elem *elems, uint64_t elem_cap, uint8_t *arena, uint64_t *scratch,
-                                       uint64_t *sums, uint64_t *zero, uint64_t nzero, uint64_t data_cap,
-                                       rr_totals *totals, hipStream_t stream, int first_only, unsigned flags) {
-    const uint32_t zraw = flags & RR_CTX_ZL_RAW ? DEC_ZL_RAW : 0u;
-    uint32_t win = dec_win(data_cap), nw = (uint32_t)(data_cap / win + 1);
-    // A small batch that fits one window per CU, at most a sort chunk (512 values) a window, gets
-    // one window per CU instead of two: config 1 at 100K values 22.0 -> 19.1 us, config 2 / 4 at
-    // 30K values -16 % / -10 %; at 200K config-1 values (781 a window) two per CU stay faster
-    // (profiles/r5_small_windows_ab.txt).  Fewer windows than dec_windows(data_cap): the scratch
-    // and the sums sized from data_cap still cover them.
-    const uint64_t cus = dev_cus();
-    if (data_cap <= cus * DEC_W && n <= cus * DEC_NW * RR_WAVE) {
-        uint64_t w = ((data_cap + cus - 1) / cus + 15) & ~15ull;
-        w = w < DEC_WMIN ? DEC_WMIN : w;
-        if (w > win) {
-            win = (uint32_t)w;
-            nw = (uint32_t)(data_cap / win + 1);
-        }
-    }
-    // A batch of one generation of windows: one launch (decode_kernel's ONE form) instead of
-    // count_kernel + decode_kernel.  (The debug hook that withholds the second launch keeps the
-    // two-launch form, which it tests.)
-    uint64_t *wtot = sums;
-    uint64_t *gtot = wtot + nw;
-    uint32_t *counts = reinterpret_cast<uint32_t *>(scratch + RR_SCRATCH_HDR);
-    uint32_t *first_val = counts + ((n + 2) & ~1ull);
-    uint64_t *first_off = reinterpret_cast<uint64_t *>(first_val + ((nw + 2) & ~1u));
-    uint8_t *cls = reinterpret_cast<uint8_t *>(first_off + nw + 1);
-    if (first_only != 1 && nw <= dec_slots() && nw <= DEC_NW * RR_WAVE && dec_one()) {   // (a look-back thread per earlier window)
-        hipLaunchKernelGGL((DECODE_ONE), dim3(nw), dim3(DEC_NW * RR_WAVE), 0, stream, blob, data_cap, offsets, n,
-                           nullptr, nullptr, cls, counts, nullptr, nullptr, values, elems, elem_cap, arena, nw, win,
-                           totals, sums, zero, nzero, (first_only == 2 ? DEC_HELP_ALL : 0u) | zraw);
-        return hipGetLastError();
-    }
-    if (data_cap < (1ull << 32))
-        hipLaunchKernelGGL(count_kernel<true>, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, stream, blob, offsets, n,
-                           first_val, first_off, nw, win, counts, cls, wtot, gtot, zero, nzero, totals, zraw);
-    else
-        hipLaunchKernelGGL(count_kernel<false>, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, stream, blob, offsets,
-                           n, first_val, first_off, nw, win, counts, cls, wtot, gtot, zero, nzero, totals, zraw);
-    if (first_only == 1) return hipGetLastError();
-    hipLaunchKernelGGL((DECODE_KERNEL), dim3(nw), dim3(DEC_NW * RR_WAVE), 0, stream, blob, data_cap, offsets, n,
-                       first_val, first_off, cls, counts, wtot, gtot, values, elems, elem_cap, arena, nw, win, totals,
-                       nullptr, nullptr, 0, zraw);
-    return hipGetLastError();
-}
-
 // Encode scratch (uint64 words): [HDR] [error word] [tile stats, 3 per 256 values, twice]
 // [block sums, t] [group sums, t / WGROUP + 1] [first value per output window u32, nwin+1].
 // E1's block 0 zeroes the error word and the totals.  The group sums are in the context's

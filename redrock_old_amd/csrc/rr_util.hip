@@ -3,7 +3,6 @@
 // (rr_launch_scan_u64: the snappy and lz4 kernels' block lengths).
 #include <hip/hip_runtime.h>
 
-#include "rr_decode_class.h"   // make_rsrc
 #include "rr_device.h"
 #include "rr_kernels.h"
 
@@ -128,7 +127,7 @@ __global__ __launch_bounds__(NT) void copy_kernel(const uint8_t *__restrict__ sr
     for (uint64_t base = (uint64_t)blockIdx.x * TILE; base < bytes; base += (uint64_t)gridDim.x * TILE) {
         const uint64_t left = bytes - base;
         const uint32_t span = left < TILE ? (uint32_t)left : (uint32_t)TILE;
-        const rsrc_t RS = make_rsrc(src + base, span), RD = make_rsrc(dst + base, span);
+        const rsrc_t RS = mk_rsrc(src + base, span), RD = mk_rsrc(dst + base, span);
         u32x4 x[U];
 #pragma unroll
         for (uint32_t k = 0; k < U; ++k)

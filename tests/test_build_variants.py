@@ -58,6 +58,33 @@ def test_every_knob_has_a_variant():
     assert len(knobs) <= 16, sorted(knobs)
 
 
+def _with_headers(src, seen=None):
+    """src and the project headers it includes, directly or through one of them."""
+    seen = set() if seen is None else seen
+    if src not in seen and os.path.exists(os.path.join(CSRC, src)):
+        seen.add(src)
+        with open(os.path.join(CSRC, src)) as f:
+            for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M):
+                _with_headers(os.path.normpath(inc), seen)
+    return seen
+
+
+def _untested(src, flags):
+    """The -DRR_X of flags that neither src nor a project header it includes tests in a preprocessor line."""
+    tested = set().union(*map(_knobs, _with_headers(src)))
+    return set(re.findall(r"-D(RR_[A-Z0-9_]+)", flags)) - tested
+
+
+def test_every_variant_sets_a_knob_its_source_tests():
+    """A variant compiled against a file that never looks at its -D would prove nothing."""
+    for src, flags in VARIANTS:
+        assert not _untested(src, flags), (src, flags)
+    # (the check itself: a variant pointed at the wrong file is found)
+    assert _untested("rr_snappy.hip", "-DRR_DEC_W=65536 -DRR_PROBE") == {"RR_DEC_W"}
+    assert _untested("rr_kernels.hip", "-DRR_SNZ_K=1") == {"RR_SNZ_K"}
+    assert _untested("rr_util.hip", "-DRR_ABLATE=4") == {"RR_ABLATE"}
+
+
 @pytest.mark.skipif(not os.path.exists(HIPCC) or shutil.which("clang") is None and not os.path.exists(HIPCC),
                     reason="hipcc not installed")
 @pytest.mark.parametrize("src,flags", VARIANTS, ids=[f"{s}:{f}" for s, f in VARIANTS])
