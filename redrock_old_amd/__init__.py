@@ -95,6 +95,25 @@ class RdbFileRepl(C.Structure):
     _fields_ = [("stream_db", C.c_int32), ("replid", C.c_char_p), ("offset", C.c_int64)]
 
 
+class RdbReadState(C.Structure):
+    """rr_rdbread_state (include/rr_rdbread.h): zeroed before the first rr_rdbread_index call."""
+    _fields_ = [("version", C.c_uint32), ("rsv", C.c_uint32), ("db", C.c_uint64), ("pos", C.c_uint64)]
+
+
+class RdbReadIndexResult(C.Structure):
+    _fields_ = [("n_recs", C.c_uint64), ("n_items", C.c_uint64), ("eof_at", C.c_uint64), ("cksum", C.c_uint64),
+                ("err_at", C.c_uint64), ("has_cksum", C.c_uint32), ("rsv", C.c_uint32)]
+
+
+class RdbReadOut(C.Structure):
+    """rr_rdbread_out: device pointers for rr_rdbread_split, host ones for _host."""
+    _fields_ = [("keys", BlobBatch), ("payloads", BlobBatch), ("types", C.c_void_p), ("expires", C.c_void_p),
+                ("idle", C.c_void_p), ("freq", C.c_void_p), ("status", C.c_void_p)]
+
+
+RDBREAD_ITEM_DT = np.dtype([("opcode", "<u4"), ("rsv", "<u4"), ("at", "<u8"), ("end", "<u8")])   # rr_rdbread_item
+
+
 class Shard(C.Structure):
     _fields_ = [("v0", C.c_uint64), ("v1", C.c_uint64), ("b0", C.c_uint64), ("b1", C.c_uint64)]
 
@@ -161,6 +180,14 @@ RDBFILE_E_VALUE, RDBFILE_E_KEY, RDBDUMP_E_SHORT, RDBDUMP_E_VERSION, RDBDUMP_E_CR
 # the CRC kernels' shape (rr_rdbfile.h): bytes a lane, bytes a wave and step, waves a launch at most
 CRC64_RUN, CRC64_PIECE, CRC64_MAX_WAVES = 256, 64 * 256, 2048
 RDBDUMP_MAX_WAVES = 16384       # rr_rdbdump_batch / rr_rdbdump_verify_batch: a wave a value
+# include/rr_rdbread.h (reading a complete RDB stream: host record index, GPU split and checksum verdict)
+RDBREAD_EXPORTS = ["rr_rdbread_index", "rr_rdbread_string", "rr_rdbread_len", "rr_rdbread_split", "rr_rdbread_split_host",
+                   "rr_rdbread_verify", "rr_rdbread_verify_host"]
+RDBREAD_DONE, RDBREAD_MORE, RDBREAD_FULL = 0, 1, 2
+RDBREAD_E_SLICE, RDBREAD_E_TRUNC, RDBREAD_E_OPCODE, RDBREAD_E_KEY, RDBREAD_NO_CKSUM = 46, 47, 48, 49, 50
+RDBREAD_E_MAGIC, RDBREAD_E_VERSION, RDBREAD_E_UNSUPPORTED, RDBREAD_E_LEN = 51, 52, 53, 54
+# the split's shape (rr_rdbread.h): waves a launch at most, bytes a lane copies a step, bytes a wave and step
+RDBREAD_MAX_WAVES, RDBREAD_LANE_BYTES, RDBREAD_WAVE_STEP = 16384, 16, 64 * 16
 API_EINVAL = -1                 # RR_API_EINVAL (rr_serdes.h)
 SNAPPY_STATUS = {0: "OK", 1: "HEADER", 2: "TRUNC", 3: "OFFSET", 4: "OVERFLOW", 5: "LENGTH", 6: "CAPACITY"}
 LZ4_STATUS = dict(SNAPPY_STATUS)   # RR_LZ4_* parallel RR_SNAPPY_*
@@ -279,6 +306,14 @@ def lib():
         L.rr_crc64_shift.restype = u64
         L.rr_crc64_mul.argtypes = [u64, u64]
         L.rr_crc64_mul.restype = u64
+    if "RR_LIB" not in os.environ or hasattr(L, "rr_rdbread_split"):   # (RR_LIB: an older build may predate them)
+        L.rr_rdbread_index.argtypes = [C.POINTER(RdbReadState), vp, u64, vp, vp, vp, u64, vp, u64, C.POINTER(RdbReadIndexResult)]
+        L.rr_rdbread_string.argtypes = [vp, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+        L.rr_rdbread_len.argtypes = [vp, u64, u64, C.POINTER(u64), C.POINTER(u64)]
+        L.rr_rdbread_split.argtypes = [vp, vp, u64, vp, vp, u64, C.c_uint32, C.POINTER(RdbReadOut), vp, vp]
+        L.rr_rdbread_split_host.argtypes = [vp, vp, u64, vp, vp, u64, C.c_uint32, C.POINTER(RdbReadOut), C.POINTER(RdbFileResult)]
+        L.rr_rdbread_verify.argtypes = [vp, vp, u64, u64, vp, vp, vp]
+        L.rr_rdbread_verify_host.argtypes = [vp, vp, u64, u64, vp, C.POINTER(RdbFileResult)]
     if hasattr(L, "rr_host_decode_batch"):   # (RR_LIB: an older build for A/B timing may predate it)
         L.rr_host_reserve.argtypes = [vp, u64]
         L.rr_host_reserve.restype = u64
@@ -857,6 +892,62 @@ class Engine:
                                                     _ptr(ty), _ptr(st), C.byref(res)))
         return out[:min(int(oo[-1]), out_cap)], oo, ty[:n], st[:n], res.as_dict()
 
+    # ---- reading a complete RDB stream (include/rr_rdbread.h) ---------------------------------------
+    def rdbread_split(self, data, rec_start, rec_end, version: int, key_data, key_offsets, pay_data, pay_offsets, types,
+                      expires, idle, freq, status, result, stream=None, data_cap: int | None = None,
+                      key_cap: int | None = None, pay_cap: int | None = None):
+        """rr_rdbread_split on torch CUDA tensors; no host sync.  rec_start / rec_end: int64[n] (rr_rdbread_index's);
+        expires / idle: int64[n], freq: int16[n], result: uint8[24].  key_data / pay_data may be empty (sizes only);
+        *_cap default to the tensors' sizes."""
+        n = _n_offsets(key_offsets)
+        dp = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        out = RdbReadOut(BlobBatch(dp(key_data), key_offsets.data_ptr(), n, key_data.numel() if key_cap is None else key_cap),
+                         BlobBatch(dp(pay_data), pay_offsets.data_ptr(), n, pay_data.numel() if pay_cap is None else pay_cap),
+                         dp(types), dp(expires), dp(idle), dp(freq), dp(status))
+        _check(self._L.rr_rdbread_split(self._ctx, dp(data), data.numel() if data_cap is None else data_cap, dp(rec_start),
+                                        dp(rec_end), n, version, C.byref(out), result.data_ptr(), _sp(stream)))
+
+    def rdbread_split_host(self, data, rec_start, rec_end, version: int, key_cap: int | None = None, pay_cap: int | None = None):
+        """rr_rdbread_split_host over numpy arrays: dict(key_data, key_offsets, pay_data, pay_offsets, types, expires,
+        idle, freq, status, result).  A cap of None: asks for the sizes first (a call with both caps 0)."""
+        data = np.ascontiguousarray(data, np.uint8)
+        rs, re_ = np.ascontiguousarray(rec_start, np.uint64), np.ascontiguousarray(rec_end, np.uint64)
+        n = len(rs)
+        ko, po = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+        m = max(n, 1)
+        ty, st = np.zeros(m, np.uint8), np.zeros(m, np.uint8)
+        ex, idl, fq = np.zeros(m, np.int64), np.zeros(m, np.uint64), np.zeros(m, np.int16)
+        res = RdbFileResult()
+
+        def call(kd, kc, pd, pc):
+            out = RdbReadOut(BlobBatch(_ptr(kd) if kc else None, _ptr(ko), n, kc), BlobBatch(_ptr(pd) if pc else None, _ptr(po), n, pc),
+                             _ptr(ty), _ptr(ex), _ptr(idl), _ptr(fq), _ptr(st))
+            _check(self._L.rr_rdbread_split_host(self._ctx, _ptr(data), data.size, _ptr(rs), _ptr(re_), n, version, C.byref(out),
+                                                 C.byref(res)))
+
+        if key_cap is None or pay_cap is None:
+            call(None, 0, None, 0)
+            key_cap = int(ko[-1]) if key_cap is None else key_cap
+            pay_cap = int(po[-1]) if pay_cap is None else pay_cap
+        kd, pd = np.zeros(max(key_cap, 1), np.uint8), np.zeros(max(pay_cap, 1), np.uint8)
+        call(kd, key_cap, pd, pay_cap)
+        return dict(key_data=kd[:min(int(ko[-1]), key_cap)], key_offsets=ko, pay_data=pd[:min(int(po[-1]), pay_cap)],
+                    pay_offsets=po, types=ty[:n], expires=ex[:n], idle=idl[:n], freq=fq[:n], status=st[:n], result=res.as_dict())
+
+    def rdbread_verify(self, data, eof_at: int, state, result, stream=None, data_cap: int | None = None):
+        """rr_rdbread_verify on torch CUDA tensors; no host sync.  state: int64[2] (checksum in and out, the bytes
+        summed), result: uint8[24] (status: 0, RDBDUMP_E_CRC or RDBREAD_NO_CKSUM)."""
+        _check(self._L.rr_rdbread_verify(self._ctx, data.data_ptr(), data.numel() if data_cap is None else data_cap, eof_at,
+                                         state.data_ptr(), result.data_ptr(), _sp(stream)))
+
+    def rdbread_verify_host(self, data, eof_at: int, crc_in: int = 0):
+        """rr_rdbread_verify_host over a numpy array: (verdict, the computed checksum)."""
+        data = np.ascontiguousarray(data, np.uint8)
+        st = np.array([crc_in, 0], np.uint64)
+        res = RdbFileResult()
+        _check(self._L.rr_rdbread_verify_host(self._ctx, _ptr(data), data.size, eof_at, _ptr(st), C.byref(res)))
+        return int(res.status), int(st[0])
+
     def encode_device(self, values, elems, arena, out_data, out_offsets, totals, stream=None):
         n = out_offsets.numel() - 1
         inb = FlatBatch(values.data_ptr(), elems.data_ptr(), arena.data_ptr(), n, elems.numel() // 16,
@@ -982,3 +1073,51 @@ def rdbfile_selectdb(dbid: int, db_size: int, expires_size: int, cap: int = 32):
     buf = np.full(max(cap, 1), 0xA5, np.uint8)
     need = int(lib().rr_rdbfile_selectdb(_ptr(buf), cap, dbid, db_size, expires_size))
     return need, buf[:cap].tobytes()
+
+
+# ---- include/rr_rdbread.h: the record index and the host string reader (no GPU) -------------------
+def rdbread_index(buf, state: RdbReadState | None = None, max_recs: int | None = None, max_items: int | None = None):
+    """rr_rdbread_index over buf from state.pos (a fresh state when None): dict(rc, rec_start, rec_end, rec_db, items
+    (RDBREAD_ITEM_DT), eof_at, cksum, has_cksum, err_at, state).  max_* None: room for every byte of buf."""
+    b = np.frombuffer(bytes(buf), np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf, np.uint8)
+    st = state if state is not None else RdbReadState()
+    max_recs = b.size if max_recs is None else max_recs
+    max_items = b.size if max_items is None else max_items
+    rs, re_, rd = (np.zeros(max(max_recs, 1), np.uint64) for _ in range(3))
+    items = np.zeros(max(max_items, 1), RDBREAD_ITEM_DT)
+    res = RdbReadIndexResult()
+    rc = int(lib().rr_rdbread_index(C.byref(st), _ptr(b), b.size, _ptr(rs), _ptr(re_), _ptr(rd), max_recs, _ptr(items), max_items,
+                                    C.byref(res)))
+    if rc < 0:
+        raise RRError(f"rr_rdbread_index failed ({rc})")
+    nr, ni = int(res.n_recs), int(res.n_items)
+    return dict(rc=rc, rec_start=rs[:nr], rec_end=re_[:nr], rec_db=rd[:nr], items=items[:ni], eof_at=int(res.eof_at),
+                cksum=int(res.cksum), has_cksum=bool(res.has_cksum), err_at=int(res.err_at), state=st)
+
+
+def rdbread_string(buf, at: int, out_cap: int | None = None):
+    """rr_rdbread_string: (rc, the string's bytes or None, its length, the offset behind it).  out_cap None: the
+    length first."""
+    b = np.frombuffer(bytes(buf), np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf, np.uint8)
+    ln, end = C.c_uint64(0), C.c_uint64(0)
+    L = lib()
+    if out_cap is None:
+        rc = int(L.rr_rdbread_string(_ptr(b), b.size, at, None, 0, C.byref(ln), C.byref(end)))
+        if rc not in (RDBREAD_DONE, E_CAPACITY):
+            return rc, None, int(ln.value), int(end.value)
+        out_cap = int(ln.value)
+    out = np.full(out_cap + 8, 0xA5, np.uint8)
+    rc = int(L.rr_rdbread_string(_ptr(b), b.size, at, _ptr(out), out_cap, C.byref(ln), C.byref(end)))
+    assert (out[out_cap:] == 0xA5).all()
+    if rc != RDBREAD_DONE:
+        assert (out == 0xA5).all()
+        return rc, None, int(ln.value), int(end.value)
+    return rc, out[:int(ln.value)].tobytes(), int(ln.value), int(end.value)
+
+
+def rdbread_len(buf, at: int):
+    """rr_rdbread_len: (rc, the number, the offset behind it)."""
+    b = np.frombuffer(bytes(buf), np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf, np.uint8)
+    val, end = C.c_uint64(0), C.c_uint64(0)
+    rc = int(lib().rr_rdbread_len(_ptr(b), b.size, at, C.byref(val), C.byref(end)))
+    return rc, int(val.value), int(end.value)

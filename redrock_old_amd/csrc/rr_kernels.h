@@ -124,6 +124,17 @@ hipError_t rr_launch_rdbdump(const uint8_t *data, uint64_t in_cap, const uint64_
 hipError_t rr_launch_rdbdump_verify(const uint8_t *data, uint64_t in_cap, const uint64_t *in_offs, uint64_t n, uint8_t *out,
                                     uint64_t out_cap, uint64_t *out_offs, uint8_t *types, uint8_t *status, uint64_t *scratch,
                                     struct rr_rdbfile_result *result, hipStream_t stream);
+/* rr_rdbread.hip (include/rr_rdbread.h).  The split: sizes, one scan over key sizes | payload sizes,
+ * emit; a wave a record, at most RR_RDBREAD_MAX_WAVES waves; every pointer of *out on the device,
+ * scratch of rr_rdbread_scratch_words(n).  The verdict: state[0] against the 8 bytes at ck, into
+ * *result (bytes as given). */
+struct rr_rdbread_out;
+uint64_t rr_rdbread_scratch_words(uint64_t n);
+hipError_t rr_launch_rdbread_split(const uint8_t *data, uint64_t data_cap, const uint64_t *rec_start, const uint64_t *rec_end,
+                                   uint64_t n, const struct rr_rdbread_out *out, uint64_t *scratch,
+                                   struct rr_rdbfile_result *result, hipStream_t stream);
+hipError_t rr_launch_rdbread_verdict(const uint8_t *ck, uint64_t bytes, const uint64_t *state, struct rr_rdbfile_result *result,
+                                     hipStream_t stream);
 
 #ifdef __cplusplus
 }
