@@ -171,6 +171,13 @@ RDBCONVERT_EXPORTS = ["rr_rdbconvert_bound", "rr_rdbconvert_batch", "rr_rdbconve
 RDBCONVERT_SKIP = 45            # not attempted: load_status != RDBLOAD_E_CONVERT
 RDBCONVERT_MAX_N = 512          # the most members of a Set or ZSet that is sorted
 RDBCONVERT_MAX_WAVES = 16384    # a wave an attempted value, a grid stride beyond
+# include/rr_d2string.h (d2string with an exact %.17g, host and GPU)
+D2STRING_EXPORTS = ["rr_d2string", "rr_d2string_batch", "rr_d2string_batch_host"]
+D2STRING_MAX = 24               # the longest text: "-4.9406564584124654e-324"
+D2STRING_SLOT = 32              # the batch calls' bytes per text
+# include/rr_rdbzset.h (the small ZSets rdbconvert left because a score needs %.17g)
+RDBZSET_EXPORTS = ["rr_rdbzset_bound", "rr_rdbzset_batch", "rr_rdbzset_batch_host"]
+RDBZSET_SKIP = 55               # not attempted: not a ZSET_2 that rdbconvert left at RDBLOAD_E_CONVERT
 # include/rr_rdbfile.h (RDB stream framing, DUMP payloads and their CRC-64 around the payloads above)
 RDBFILE_EXPORTS = ["rr_rdbfile_bound", "rr_rdbfile_section", "rr_rdbfile_section_host", "rr_crc64_device",
                    "rr_rdbdump_batch", "rr_rdbdump_batch_host", "rr_rdbdump_verify_batch", "rr_rdbdump_verify_batch_host",
@@ -285,6 +292,14 @@ def lib():
                                           C.POINTER(RdbLoadOpts), vp]
         L.rr_rdbconvert_batch_host.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(RdbLoadOpts), vp, u64, vp, vp, vp,
                                                C.POINTER(Totals)]
+    if "RR_LIB" not in os.environ or hasattr(L, "rr_rdbzset_batch"):   # (RR_LIB: an older build may predate them)
+        L.rr_d2string.argtypes = [vp, C.c_double]
+        L.rr_d2string_batch.argtypes = [vp, vp, u64, vp, vp, vp]
+        L.rr_d2string_batch_host.argtypes = [vp, vp, u64, vp, vp]
+        L.rr_rdbzset_bound.argtypes = [u64, u64]
+        L.rr_rdbzset_bound.restype = u64
+        L.rr_rdbzset_batch.argtypes = [vp, C.POINTER(BlobBatch), vp, vp, C.POINTER(BlobBatch), vp, vp, C.POINTER(RdbLoadOpts), vp]
+        L.rr_rdbzset_batch_host.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(RdbLoadOpts), vp, u64, vp, vp, C.POINTER(Totals)]
     if "RR_LIB" not in os.environ or hasattr(L, "rr_rdbfile_section"):   # (RR_LIB: an older build may predate them)
         L.rr_rdbfile_bound.argtypes = [u64, u64, u64, u64]
         L.rr_rdbfile_bound.restype = u64
@@ -800,6 +815,56 @@ class Engine:
                                            C.c_void_p(status.data_ptr()), C.c_void_p(totals.data_ptr()),
                                            C.byref(opts) if opts is not None else None, _sp(stream)))
 
+    # ---- small ZSets with fractional scores (include/rr_d2string.h, include/rr_rdbzset.h) ---------
+    def d2string_host(self, bits: np.ndarray, fill: int = 0):
+        """rr_d2string_batch_host: the GPU's d2string of the doubles with these bits (uint64) -> (text
+        uint8[n, 32], len uint8[n]).  The slots are pre-filled with `fill`; bytes past len keep it."""
+        bits = np.ascontiguousarray(bits, np.uint64)
+        n = len(bits)
+        text = np.full((max(n, 1), D2STRING_SLOT), fill, np.uint8)
+        ln = np.zeros(max(n, 1), np.uint8)
+        _check(self._L.rr_d2string_batch_host(self._ctx, _ptr(bits), n, _ptr(text), _ptr(ln)))
+        return text[:n], ln[:n]
+
+    def d2string(self, bits, text, length, stream=None):
+        """rr_d2string_batch on torch CUDA tensors (bits int64[n], text uint8[32 n], length uint8[n]); no host sync."""
+        n = bits.numel()
+        dp = lambda t: t.data_ptr() if t.numel() else None
+        _check(self._L.rr_d2string_batch(self._ctx, dp(bits), n, dp(text), dp(length), _sp(stream)))
+
+    def rdbzset_host(self, data: np.ndarray, offsets: np.ndarray, types: np.ndarray, convert_status: np.ndarray,
+                     opts: RdbLoadOpts | None = None, out_cap: int | None = None):
+        """RDB payloads and rdbconvert's status -> (blob data, offsets, status, totals): the ZSET_ZIPLIST
+        blobs of the ZSET_2 values rdbconvert left with RDBLOAD_E_CONVERT.  out_cap None: asks for the size first."""
+        n = len(offsets) - 1
+        data = np.ascontiguousarray(data, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        types = np.ascontiguousarray(types, np.uint8)
+        convert_status = np.ascontiguousarray(convert_status, np.uint8)
+        out_offsets = np.zeros(n + 1, np.uint64)
+        status = np.zeros(max(n, 1), np.uint8)
+        t = Totals()
+        po = C.byref(opts) if opts is not None else None
+        if out_cap is None:
+            _check(self._L.rr_rdbzset_batch_host(self._ctx, _ptr(data), _ptr(offsets), _ptr(types), _ptr(convert_status), n, po,
+                                                 None, 0, _ptr(out_offsets), _ptr(status), C.byref(t)))
+            out_cap = int(out_offsets[-1])
+        out = np.zeros(max(out_cap, 1), np.uint8)
+        _check(self._L.rr_rdbzset_batch_host(self._ctx, _ptr(data), _ptr(offsets), _ptr(types), _ptr(convert_status), n, po,
+                                             _ptr(out), out_cap, _ptr(out_offsets), _ptr(status), C.byref(t)))
+        return out[:min(int(out_offsets[-1]), out_cap)], out_offsets, status[:n], t.as_dict()
+
+    def rdbzset(self, data, offsets, types, convert_status, out_data, out_offsets, status, totals,
+                opts: RdbLoadOpts | None = None, stream=None):
+        """rr_rdbzset_batch on torch CUDA tensors; no host sync.  out_data may be empty (sizes only)."""
+        n = out_offsets.numel() - 1
+        inb = BlobBatch(data.data_ptr() if data.numel() else None, offsets.data_ptr(), n, data.numel())
+        outb = BlobBatch(out_data.data_ptr() if out_data.numel() else None, out_offsets.data_ptr(), n, out_data.numel())
+        _check(self._L.rr_rdbzset_batch(self._ctx, C.byref(inb), C.c_void_p(types.data_ptr()),
+                                        C.c_void_p(convert_status.data_ptr()), C.byref(outb), C.c_void_p(status.data_ptr()),
+                                        C.c_void_p(totals.data_ptr()), C.byref(opts) if opts is not None else None,
+                                        _sp(stream)))
+
     # ---- RDB streams and DUMP payloads with their CRC-64 (include/rr_rdbfile.h) -------------------
     def rdbfile_section(self, pay_data, pay_offsets, types, status, key_data, key_offsets, out, rec_offsets, rec_status,
                         state, result, expires=None, idle=None, freq=None, head=None, flags: int = 0, stream=None,
@@ -1032,6 +1097,18 @@ def rdbsave_bound(values: np.ndarray, elems: np.ndarray) -> int:
 def rdbload_bound(n: int, payload_bytes: int) -> int:
     """rr_rdbload_bound: an upper bound on the blob bytes of n payloads without LZF strings."""
     return int(lib().rr_rdbload_bound(n, payload_bytes))
+
+
+def d2string(v: float) -> bytes:
+    """rr_d2string: the reference's d2string of v (the host twin of the GPU's printer)."""
+    buf = C.create_string_buffer(D2STRING_MAX)
+    n = lib().rr_d2string(buf, float(v))
+    return buf.raw[:n]
+
+
+def rdbzset_bound(n: int, payload_bytes: int) -> int:
+    """rr_rdbzset_bound: an upper bound on the blob bytes of n ZSET_2 payloads converted with printed scores."""
+    return int(lib().rr_rdbzset_bound(n, payload_bytes))
 
 
 def rdbconvert_bound(n: int, payload_bytes: int) -> int:

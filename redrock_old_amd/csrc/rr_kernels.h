@@ -103,6 +103,14 @@ hipError_t rr_launch_rdbconvert(const uint8_t *data, uint64_t in_cap, const uint
                                 const uint8_t *load_status, uint64_t n, const uint32_t *opt6, uint8_t *out, uint64_t out_cap,
                                 uint64_t *out_offs, uint8_t *out_types, uint8_t *status, uint64_t *scratch, rr_totals *totals,
                                 hipStream_t stream);
+/* rr_rdbzset.hip (include/rr_d2string.h, include/rr_rdbzset.h).  The printer: one launch, none for n ==
+ * 0.  The stage: flags, scan, compaction, sizes, scan, emit; scratch of rr_rdbzset_scratch_words(n);
+ * opt6 as for rr_launch_rdbload */
+hipError_t rr_launch_d2string(const uint64_t *bits, uint64_t n, uint8_t *text, uint8_t *len, hipStream_t stream);
+uint64_t rr_rdbzset_scratch_words(uint64_t n);
+hipError_t rr_launch_rdbzset(const uint8_t *data, uint64_t in_cap, const uint64_t *in_offs, const uint8_t *types,
+                             const uint8_t *convert_status, uint64_t n, const uint32_t *opt6, uint8_t *out, uint64_t out_cap,
+                             uint64_t *out_offs, uint8_t *status, uint64_t *scratch, rr_totals *totals, hipStream_t stream);
 /* rr_rdbfile.hip (include/rr_rdbfile.h).  The CRC kernels' shape is RR_CRC64_RUN bytes a lane,
  * RR_CRC64_PIECE bytes a wave and step, at most RR_CRC64_MAX_WAVES waves (rr_rdbfile.h, mirrored in
  * the Python binding).  The section: sizes, scan, emit, CRC, combine; every pointer of *in on the
