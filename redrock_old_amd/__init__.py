@@ -178,6 +178,12 @@ D2STRING_SLOT = 32              # the batch calls' bytes per text
 # include/rr_rdbzset.h (the small ZSets rdbconvert left because a score needs %.17g)
 RDBZSET_EXPORTS = ["rr_rdbzset_bound", "rr_rdbzset_batch", "rr_rdbzset_batch_host"]
 RDBZSET_SKIP = 55               # not attempted: not a ZSET_2 that rdbconvert left at RDBLOAD_E_CONVERT
+# include/rr_aof.h (flat batch -> AOF rewrite commands, the AOF half of row f4)
+AOF_EXPORTS = ["rr_aof_bound", "rr_aof_select", "rr_aof_score_text", "rr_aof_batch", "rr_aof_batch_host"]
+AOF_E_CPU = 56                  # left to the CPU path: a ZLRAW-only ziplist, a score text that is not taken
+AOF_ITEMS_PER_CMD = 64          # AOF_REWRITE_ITEMS_PER_CMD
+AOF_MAX_WAVES = 16384           # a wave a value, a grid stride beyond
+AOF_SCORE_TEXT_MAX = 40         # the longest score text taken
 # include/rr_rdbfile.h (RDB stream framing, DUMP payloads and their CRC-64 around the payloads above)
 RDBFILE_EXPORTS = ["rr_rdbfile_bound", "rr_rdbfile_section", "rr_rdbfile_section_host", "rr_crc64_device",
                    "rr_rdbdump_batch", "rr_rdbdump_batch_host", "rr_rdbdump_verify_batch", "rr_rdbdump_verify_batch_host",
@@ -300,6 +306,13 @@ def lib():
         L.rr_rdbzset_bound.restype = u64
         L.rr_rdbzset_batch.argtypes = [vp, C.POINTER(BlobBatch), vp, vp, C.POINTER(BlobBatch), vp, vp, C.POINTER(RdbLoadOpts), vp]
         L.rr_rdbzset_batch_host.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(RdbLoadOpts), vp, u64, vp, vp, C.POINTER(Totals)]
+    if "RR_LIB" not in os.environ or hasattr(L, "rr_aof_batch"):   # (RR_LIB: an older build may predate them)
+        L.rr_aof_bound.argtypes = [u64, u64, u64, u64]
+        L.rr_aof_bound.restype = u64
+        L.rr_aof_select.argtypes = [vp, u64, C.c_int]
+        L.rr_aof_score_text.argtypes = [vp, C.c_char_p, u64]
+        L.rr_aof_batch.argtypes = [vp, C.POINTER(FlatBatch), C.POINTER(BlobBatch), vp, C.POINTER(BlobBatch), vp, vp, vp]
+        L.rr_aof_batch_host.argtypes = [vp, vp, vp, u64, vp, u64, u64, vp, vp, u64, vp, vp, u64, vp, vp, C.POINTER(Totals)]
     if "RR_LIB" not in os.environ or hasattr(L, "rr_rdbfile_section"):   # (RR_LIB: an older build may predate them)
         L.rr_rdbfile_bound.argtypes = [u64, u64, u64, u64]
         L.rr_rdbfile_bound.restype = u64
@@ -865,6 +878,47 @@ class Engine:
                                         C.c_void_p(totals.data_ptr()), C.byref(opts) if opts is not None else None,
                                         _sp(stream)))
 
+    # ---- AOF rewrite commands (include/rr_aof.h) --------------------------------------------------
+    def aof_host(self, values: np.ndarray, elems: np.ndarray, arena: np.ndarray, key_data, key_offsets, expires=None,
+                 data_cap: int | None = None, key_bytes: int | None = None):
+        """Flat batch and keys -> (data, offsets, status, totals): the commands rewriteAppendOnlyFileRio writes
+        per value.  expires: ms, -1 none (None: no value has one).  data_cap None: asks for the size first."""
+        n = len(values)
+        values = np.ascontiguousarray(values, VALUE_DT)
+        elems = np.ascontiguousarray(elems, ELEM_DT)
+        arena = np.ascontiguousarray(arena, np.uint8)
+        key_data = np.ascontiguousarray(key_data, np.uint8)
+        key_offsets = np.ascontiguousarray(key_offsets, np.uint64)
+        expires = None if expires is None else np.ascontiguousarray(expires, np.int64)
+        kb = key_data.size if key_bytes is None else key_bytes
+        offsets = np.zeros(n + 1, np.uint64)
+        status = np.zeros(max(n, 1), np.uint8)
+        t = Totals()
+
+        def call(data, cap):
+            _check(self._L.rr_aof_batch_host(self._ctx, _ptr(values), _ptr(elems), len(elems), _ptr(arena), arena.size, n,
+                                             _ptr(key_data), _ptr(key_offsets), kb, _ptr(expires) if expires is not None else None,
+                                             _ptr(data) if data is not None else None, cap, _ptr(offsets), _ptr(status),
+                                             C.byref(t)))
+        if data_cap is None:
+            call(None, 0)
+            data_cap = int(offsets[-1])
+        data = np.zeros(max(data_cap, 1), np.uint8)
+        call(data, data_cap)
+        return data[:min(int(offsets[-1]), data_cap)], offsets, status[:n], t.as_dict()
+
+    def aof(self, values, elems, arena, key_data, key_offsets, out_data, out_offsets, status, totals, expires=None,
+            stream=None, key_cap: int | None = None, out_cap: int | None = None):
+        """rr_aof_batch on torch CUDA tensors (uint8 views of the flat records; expires int64 or None); no
+        host sync.  out_data may be empty (sizes only); *_cap default to the tensors' sizes."""
+        n = out_offsets.numel() - 1
+        dp = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        inb = FlatBatch(values.data_ptr(), elems.data_ptr(), arena.data_ptr(), n, elems.numel() // 16, arena.numel())
+        kb = BlobBatch(dp(key_data), key_offsets.data_ptr(), n, key_data.numel() if key_cap is None else key_cap)
+        outb = BlobBatch(dp(out_data), out_offsets.data_ptr(), n, out_data.numel() if out_cap is None else out_cap)
+        _check(self._L.rr_aof_batch(self._ctx, C.byref(inb), C.byref(kb), dp(expires), C.byref(outb), dp(status),
+                                    C.c_void_p(totals.data_ptr()), _sp(stream)))
+
     # ---- RDB streams and DUMP payloads with their CRC-64 (include/rr_rdbfile.h) -------------------
     def rdbfile_section(self, pay_data, pay_offsets, types, status, key_data, key_offsets, out, rec_offsets, rec_status,
                         state, result, expires=None, idle=None, freq=None, head=None, flags: int = 0, stream=None,
@@ -1104,6 +1158,27 @@ def d2string(v: float) -> bytes:
     buf = C.create_string_buffer(D2STRING_MAX)
     n = lib().rr_d2string(buf, float(v))
     return buf.raw[:n]
+
+
+def aof_bound(n: int, n_elems: int, payload_bytes: int, key_bytes: int) -> int:
+    """rr_aof_bound: an upper bound on a batch's command bytes (include/rr_aof.h)."""
+    return int(lib().rr_aof_bound(n, n_elems, payload_bytes, key_bytes))
+
+
+def aof_select(dbi: int) -> bytes:
+    """rr_aof_select: the SELECT command rewriteAppendOnlyFileRio writes in front of db dbi."""
+    buf = C.create_string_buffer(48)
+    n = lib().rr_aof_select(buf, 48, dbi)
+    if n <= 0:
+        raise RRError(f"rr_aof_select({dbi}) failed")
+    return buf.raw[:n]
+
+
+def aof_score_text(text: bytes):
+    """rr_aof_score_text: %.17g of the score a ziplist string entry holds, or None for a text that is not taken."""
+    buf = C.create_string_buffer(32)
+    n = lib().rr_aof_score_text(buf, bytes(text), len(text))
+    return None if n < 0 else buf.raw[:n]
 
 
 def rdbzset_bound(n: int, payload_bytes: int) -> int:

@@ -111,6 +111,13 @@ uint64_t rr_rdbzset_scratch_words(uint64_t n);
 hipError_t rr_launch_rdbzset(const uint8_t *data, uint64_t in_cap, const uint64_t *in_offs, const uint8_t *types,
                              const uint8_t *convert_status, uint64_t n, const uint32_t *opt6, uint8_t *out, uint64_t out_cap,
                              uint64_t *out_offs, uint8_t *status, uint64_t *scratch, rr_totals *totals, hipStream_t stream);
+/* rr_aof.hip (include/rr_aof.h): sizes, scan, emit; scratch of rr_aof_scratch_words(n).  expires may
+ * be NULL; every other pointer on the device */
+uint64_t rr_aof_scratch_words(uint64_t n);
+hipError_t rr_launch_aof(const rr_value *values, const rr_elem *elems, uint64_t elem_cap, const uint8_t *arena,
+                         uint64_t arena_cap, uint64_t n, const uint8_t *keys, const uint64_t *key_offs, uint64_t key_cap,
+                         const int64_t *expires, uint8_t *out, uint64_t cap, uint64_t *offsets, uint8_t *status,
+                         uint64_t *scratch, rr_totals *totals, hipStream_t stream);
 /* rr_rdbfile.hip (include/rr_rdbfile.h).  The CRC kernels' shape is RR_CRC64_RUN bytes a lane,
  * RR_CRC64_PIECE bytes a wave and step, at most RR_CRC64_MAX_WAVES waves (rr_rdbfile.h, mirrored in
  * the Python binding).  The section: sizes, scan, emit, CRC, combine; every pointer of *in on the
