@@ -15,6 +15,7 @@ import redrock_old_amd as rr
 from oracle import cpu
 
 import aof_reference as ar
+from aof_shapes import HALFWAY, REFUSED                   # the two lists, shared with the device's shapes
 import rdb_reference as ref
 import rdbzset_reference as zr
 from helpers import batch_from_blobs, golden
@@ -119,19 +120,6 @@ def test_score_text_random_mantissas():
         else:
             t = "%d.e%d" % (m, e)
         assert rr.aof_score_text(t.encode()) == g17(t), t
-
-
-HALFWAY = ["9007199254740993", "9007199254740992", "9007199254740994", "9007199254740995", "18014398509481990",
-           "4.9406564584124654e-324", "4.9406564584124653e-324", "4.9406564584124655e-324", "9.8813129168249309e-324",
-           "2.4703282292062328e-324", "2.4703282292062327e-324", "2.4703282292062329e-324",
-           "7.4109846876186982e-324", "7.4109846876186981e-324", "7.4109846876186983e-324",
-           "2.2250738585072014e-308", "2.2250738585072011e-308", "2.2250738585072009e-308",
-           "1.7976931348623157e308", "1.7976931348623158e308", "1.7976931348623159e308",
-           "1e309", "-1e309", "1e-400", "-1e-400", "0.1", "1.50", ".5", "5.", "1E5", "0", "-0", "0e0", "inf", "-inf",
-           "100000000000000000000", "0.00000000000000000000000000000000000001", "1e0000000000000000000000000000000005",
-           "1e99999999", "1e-99999999", "0e99999999", "00012.5000"]
-REFUSED = ["nan", "-nan", "0x10", "+1", " 1", "1 ", "1e", "1e+", "", "-", ".", "123456789012345678", "1.2345678901234567891",
-           "1" * 41, "0." + "0" * 38 + "1", "infinity", "INF", "Inf", "1.2.3", "1e5.0", "--1", "1,5", "١"]
 
 
 @pytest.mark.parametrize("t", HALFWAY)

@@ -16,6 +16,7 @@ from oracle import cpu, pyoracle
 
 import aof_reference as ar
 import flat_forge as ff
+from aof_shapes import AGGREGATES, _bits, _word, add_aggregate, capacity_batch   # noqa: F401  (shared with the edge tests)
 import rdb_reference as ref
 import rdbzset_reference as zr
 
@@ -86,39 +87,6 @@ def check(engine, values, elems, arena, names, expires=None, data_cap=None, key_
             pay += sum(d[2] for d in descs if d[0] == rr.K_STR)
     assert total <= rr.aof_bound(n, ne, pay, sum(len(k) for k in names))
     return status, totals, slices
-
-
-def _word(rng, n):
-    return bytes(rng.integers(97, 123, n, dtype=np.uint8))    # letters: never a number
-
-
-def _bits(v):
-    return struct.unpack("<Q", struct.pack("<d", v))[0]
-
-
-def add_aggregate(f, typ, cnt, k=0):
-    """One value of the aggregate encoding typ with cnt items; a ziplist's entries are mixed STR and INT."""
-    rng = f.rng
-    w = lambda: _word(rng, int(rng.integers(0, 40)))
-    if typ == rr.T_LIST_QUICKLIST:
-        return f.add(typ, 0, [w() if j % 3 else int(rng.integers(-10**6, 10**6)) for j in range(cnt)])
-    if typ == rr.T_SET_INTSET:
-        return f.add(typ, 8, [int(rng.integers(-2**62, 2**62)) for _ in range(cnt)])
-    if typ == rr.T_SET_HT:
-        return f.add(typ, 0, [b"%d" % j + w() for j in range(cnt)])
-    if typ == rr.T_HASH_HT:
-        return f.add(typ, 0, [x for j in range(cnt) for x in (b"f%d" % j + w(), w())])
-    if typ == rr.T_ZSET_SKIPLIST:
-        return f.add(typ, 0, [x for j in range(cnt) for x in (b"m%d" % j + w(), ("score", _bits((j - 7) * 0.375 + k)))])
-    zl = ("zl", pyoracle.build_ziplist([]) if cnt == 0 else _word(rng, 30))   # only an empty one's bytes are looked at
-    if typ == rr.T_HASH_ZIPLIST:
-        return f.add(typ, 0, [zl] + [x for j in range(cnt) for x in (b"f%d" % j, int(rng.integers(-300, 300)) if j % 2 else w())])
-    return f.add(typ, 0, [zl] + [x for j in range(cnt) for x in (b"m%d" % j if j % 4 else j,
-                                                                  b"%.17g" % ((j - 5) / 8) if j % 3 else j - 9)])
-
-
-AGGREGATES = (rr.T_LIST_QUICKLIST, rr.T_SET_INTSET, rr.T_SET_HT, rr.T_HASH_HT, rr.T_ZSET_SKIPLIST, rr.T_HASH_ZIPLIST,
-              rr.T_ZSET_ZIPLIST)
 
 
 def test_items_per_aggregate(engine):
@@ -253,12 +221,7 @@ def test_unsaveable_values(engine, seed):
 
 
 def test_capacity(engine):
-    f = ff.Flat(17)
-    f.add(rr.T_SET_HT, 0, [])                                 # size 0 at offset 0: fits any capacity
-    for typ in AGGREGATES:
-        add_aggregate(f, typ, 65)
-    f.add(rr.T_STRING, 0, [b"last"])
-    v, e, a = f.done()
+    v, e, a = capacity_batch()[:3]
     names = [b"k%d" % i for i in range(len(v))]
     total = int(ar.aof_batch(v, e, a, *ar.keys_of(names))[1][-1])
     st, _, _ = check(engine, v, e, a, names, data_cap=0)
