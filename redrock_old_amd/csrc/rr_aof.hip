@@ -1,12 +1,12 @@
 // rr_aof.hip — gfx950 kernels of include/rr_aof.h: flat batch -> the RESP commands
-// rewriteAppendOnlyFileRio writes (aof.c:1302-1389, :921-1135).  Three launches, as rr_rdbsave.hip:
-// aof_size_kernel (sizes into offsets[], per-value status), rr_launch_scan_u64, aof_emit_kernel.
+// rewriteAppendOnlyFileRio writes (aof.c:1302-1389, :921-1135).  The stage is rr_stage_device.h's
+// (size, scan, emit): aof_size_kernel, aof_emit_kernel.
 //
-// A wave per value in both kernels, values strided over a capped grid.  One command of up to 64 items
+// One command of up to 64 items
 // is one wave round: lane j takes item j (one descriptor, or a pair), works out its one or two bulk
 // strings and what they cost, a wave scan places the item behind the command's head, the lane writes
-// its "$len\r\n" heads, its decimals, score texts and bodies of up to 32 bytes, and longer bodies are
-// copied by the whole wave, 16 bytes a lane.  The command's head ("*argc", the verb, the key) is lane
+// its "$len\r\n" heads, its decimals and score texts, and the bodies are copy_bodies'.
+// The command's head ("*argc", the verb, the key) is lane
 // 0's, the key's bytes the whole wave's.
 //
 // A score is printed by rr_d2string_impl.h, a lane a score, and a ziplist's score entry is read by
@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rr_flat_device.h"
-#include "rr_kernels.h"
+#include "rr_stage_device.h"
 #include "../../include/rr_aof.h"
 #include "../../include/rr_d2string.h"
 
@@ -34,10 +34,8 @@ namespace {
 
 constexpr uint32_t WPB = 4;                                    // waves (values in flight) per workgroup
 constexpr uint32_t GRID_CAP = RR_AOF_MAX_WAVES / WPB;
-constexpr uint32_t SHORT_BODY = 32;                            // a body of up to this many bytes is copied by its own lane
 constexpr uint32_t SLOT = RR_D2STRING_SLOT;
 constexpr uint32_t BIG_LDS = 4 * RR_D2S_WORDS * RR_WAVE, TXT_LDS = SLOT * RR_WAVE, WAVE_LDS = BIG_LDS + TXT_LDS;
-constexpr uint64_t MAX_SLICE = 0x7FFFFFF0ull;
 static_assert(RR_D2STRING_MAX < SLOT && WPB * WAVE_LDS <= 65536, "static LDS");
 static_assert(RR_AOF_ITEMS_PER_CMD == RR_WAVE, "a command is one wave round");
 
@@ -51,17 +49,6 @@ struct Lds {
     lds_u32 *big;   // this lane's state
     lds_u8 *txt;    // this lane's slot
 };
-
-// Wave64 inclusive scan of costs below 2^40, every lane active (rr_rdbsave.hip's)
-__device__ __forceinline__ uint64_t scan_costs(uint64_t x) {
-    const uint32_t lo = wave_incl_scan_u32((uint32_t)x & 0xFFFFFFu), hi = wave_incl_scan_u32((uint32_t)(x >> 24));
-    return ((uint64_t)hi << 24) + lo;
-}
-__device__ __forceinline__ uint64_t sum_lanes(uint64_t x) {
-    const uint32_t a = wave_incl_scan_u32((uint32_t)x & 0xFFFFFFu), b = wave_incl_scan_u32((uint32_t)(x >> 24) & 0xFFFFFFu),
-                   c = wave_incl_scan_u32((uint32_t)(x >> 48));
-    return (uint64_t)rl32(a, RR_WAVE - 1) + ((uint64_t)rl32(b, RR_WAVE - 1) << 24) + ((uint64_t)rl32(c, RR_WAVE - 1) << 48);
-}
 
 // ---- rio.c:406-445 ----
 __device__ __forceinline__ uint32_t ndig(uint32_t v) { return dec_len((int64_t)v); }
@@ -94,16 +81,14 @@ __device__ __forceinline__ Bulk bulk_of(const ElemV &e) {
     return {B_BYTES, e.len, e.data};
 }
 __device__ __forceinline__ uint64_t cost_of(const Bulk &b) { return b.kind == B_NONE ? 0 : bulk_cost(b.len); }
-// writes the bulk at d but for a body of more than SHORT_BODY arena bytes, whose place is *body
-__device__ __forceinline__ uint8_t *put_bulk(uint8_t *d, const Bulk &b, const Batch &B, const Lds &Z, uint8_t *&body) {
+// writes the bulk at d but for a body of arena bytes, whose place is *body (copy_bodies)
+__device__ __forceinline__ uint8_t *put_bulk(uint8_t *d, const Bulk &b, const Lds &Z, uint8_t *&body) {
     body = nullptr;
     if (b.kind == B_NONE) return d;
     d = put_count(d, '$', b.len);
     if (b.kind == B_INT) dec_write(d, (int64_t)b.data);
     else if (b.kind == B_TEXT) {
         for (uint32_t k = 0; k < b.len; ++k) d[k] = Z.txt[k];
-    } else if (b.len <= SHORT_BODY) {
-        for (uint32_t k = 0; k < b.len; ++k) d[k] = B.arena[b.data + k];
     } else {
         body = d;
     }
@@ -239,12 +224,12 @@ __device__ uint64_t aof_value(const Batch &B, const Lds &Z, uint32_t type, uint3
             uint8_t *body0 = nullptr, *body1 = nullptr;
             if (active) {
                 uint8_t *d = out + pos + head + incl - cost;
-                d = put_bulk(d, b0, B, Z, body0);
-                put_bulk(d, b1, B, Z, body1);
+                d = put_bulk(d, b0, Z, body0);
+                put_bulk(d, b1, Z, body1);
                 pay += (b0.kind == B_BYTES ? b0.len : 0) + (b1.kind == B_BYTES ? b1.len : 0);
             }
-            wave_copy_each(body0, B.arena + b0.data, b0.len, body0 != nullptr);
-            wave_copy_each(body1, B.arena + b1.data, b1.len, body1 != nullptr);
+            copy_bodies(body0, B.arena + b0.data, b0.len, body0 != nullptr);
+            copy_bodies(body1, B.arena + b1.data, b1.len, body1 != nullptr);
         }
         pos += head + rl64(incl, RR_WAVE - 1);
     }
@@ -276,14 +261,7 @@ __device__ __forceinline__ Lds wave_lds() {
     return {(lds_u32 *)b + lane_id(), b + BIG_LDS + SLOT * lane_id()};
 }
 
-__device__ __forceinline__ bool value_ok(const uint4 &x, uint64_t elem_cap) {
-    const uint32_t vstatus = (x.x >> 16) & 0xFFFF;
-    return vstatus == RR_OK && (uint64_t)x.w + (uint64_t)x.z <= elem_cap;
-}
-__device__ __forceinline__ bool slice_ok(uint64_t o0, uint64_t o1, uint64_t cap) { return o0 <= o1 && o1 <= cap && o1 - o0 < MAX_SLICE; }
-
-// sizes into offsets[0, n), offsets[n] = 0; status; and the zeroing the other two launches rely on
-// (the scan's look-back words, the error word, the totals)
+// sizes into offsets[0, n), offsets[n] = 0; status; and the stage's zeroing
 __global__ __launch_bounds__(WPB * RR_WAVE) void aof_size_kernel(const rr_value *__restrict__ values, uint64_t n, Batch B,
                                                                  const uint64_t *__restrict__ key_offs, uint64_t key_cap,
                                                                  const int64_t *__restrict__ expires, uint64_t *__restrict__ offsets,
@@ -292,11 +270,7 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void aof_size_kernel(const rr_value 
     const Lds Z = wave_lds();
     const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
     const uint64_t gtid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (uint64_t k = gtid; k < nzero; k += nthreads) zero[k] = 0;
-    if (gtid == 0) {
-        offsets[n] = 0;
-        totals->n_elems = totals->bytes = totals->n_bad = totals->payload = 0;
-    }
+    zero_stage_words(gtid, nthreads, zero, nzero, &offsets[n], totals);
     const uint64_t nwaves = nthreads / RR_WAVE;
     uint64_t pay = 0;
     for (uint64_t v = first64(gtid / RR_WAVE); v < n; v += nwaves) {
@@ -353,17 +327,7 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void aof_emit_kernel(const rr_value 
         const int64_t ex = expires ? (int64_t)first64((uint64_t)expires[v]) : -1;
         aof_value<true>(B, Z, type, enc, rfl(x.w), rfl(x.z), keys + k0, (uint32_t)(k1 - k0), ex, out + o0, st, pay);
     }
-    pay = sum_lanes(pay);
-    if (lane_id() == 0) {
-        if (pay) atomicAdd((unsigned long long *)&totals->payload, (unsigned long long)pay);
-        if (n_el) atomicAdd((unsigned long long *)&totals->n_elems, (unsigned long long)n_el);
-        if (n_bad) atomicAdd((unsigned long long *)&totals->n_bad, (unsigned long long)n_bad);
-    }
-}
-
-uint32_t grid_for(uint64_t n) {
-    const uint64_t b = (n + WPB - 1) / WPB;
-    return (uint32_t)(b < GRID_CAP ? (b ? b : 1) : GRID_CAP);
+    add_totals(totals, sum_lanes(pay), n_el, n_bad);
 }
 
 }  // namespace
@@ -378,13 +342,14 @@ extern "C" hipError_t rr_launch_aof(const rr_value *values, const rr_elem *elems
     const uint64_t lbw = rr_scan_words(n);
     uint64_t *lb = scratch, *err = scratch + lbw;
     const Batch B = {elems, elem_cap, arena, arena_cap};
-    hipLaunchKernelGGL(aof_size_kernel, dim3(grid_for(n)), dim3(WPB * RR_WAVE), 0, stream, values, n, B, key_offs, key_cap, expires,
+    const uint32_t grid = capped_grid(n, WPB, GRID_CAP);
+    hipLaunchKernelGGL(aof_size_kernel, dim3(grid), dim3(WPB * RR_WAVE), 0, stream, values, n, B, key_offs, key_cap, expires,
                        offsets, status, lb, lbw + 1, totals);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     e = rr_launch_scan_u64(offsets, n, lb, err, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(aof_emit_kernel, dim3(grid_for(n)), dim3(WPB * RR_WAVE), 0, stream, values, n, B, keys, key_offs, expires,
+    hipLaunchKernelGGL(aof_emit_kernel, dim3(grid), dim3(WPB * RR_WAVE), 0, stream, values, n, B, keys, key_offs, expires,
                        (const uint64_t *)offsets, out, cap, status, (const uint64_t *)err, totals);
     return hipGetLastError();
 }

@@ -84,19 +84,22 @@ hipError_t rr_launch_lz4_decompress(const uint8_t *in, uint64_t in_cap, const ui
                                     hipStream_t stream);
 hipError_t rr_launch_lz4_compress(const uint8_t *in, uint64_t in_cap, const uint64_t *in_offs, uint64_t n, uint8_t *out,
                                   uint64_t *out_offs, uint64_t *scratch, uint64_t slot_bytes, hipStream_t stream);
-/* rr_rdbsave.hip (include/rr_rdbsave.h): sizes, scan, emit; scratch of rr_rdbsave_scratch_words(n,
- * lzf ? elem_cap : 0).  lzf: RR_RDBSAVE_LZF, the LZF instantiations of the size and emit kernels */
+/* The launches below are stages of one shape, rr_stage_device.h's: sizes, scan, emit ("the stage"),
+ * some with an attempted list in front (flags, scan, compaction).
+ * rr_rdbsave.hip (include/rr_rdbsave.h): the stage, then the Lists' two launches; scratch of
+ * rr_rdbsave_scratch_words(n, lzf ? elem_cap : 0).  lzf: RR_RDBSAVE_LZF, the LZF instantiations of
+ * the size and emit kernels */
 uint64_t rr_rdbsave_scratch_words(uint64_t n, uint64_t lzf_elems);
 hipError_t rr_launch_rdbsave(const rr_value *values, const rr_elem *elems, uint64_t elem_cap, const uint8_t *arena,
                              uint64_t arena_cap, uint64_t n, int list_fill, int lzf, uint8_t *out, uint64_t cap, uint64_t *offsets,
                              uint8_t *types, uint8_t *status, uint64_t *scratch, rr_totals *totals, hipStream_t stream);
-/* rr_rdbload.hip (include/rr_rdbload.h): sizes, scan, emit; scratch of rr_rdbload_scratch_words(n).
+/* rr_rdbload.hip (include/rr_rdbload.h): the stage; scratch of rr_rdbload_scratch_words(n).
  * opt6: lru & RR_LRU_MASK, then the five thresholds in rr_rdbload_opts' order */
 uint64_t rr_rdbload_scratch_words(uint64_t n);
 hipError_t rr_launch_rdbload(const uint8_t *data, uint64_t in_cap, const uint64_t *in_offs, const uint8_t *types, uint64_t n,
                              const uint32_t *opt6, uint8_t *out, uint64_t out_cap, uint64_t *out_offs, uint8_t *status,
                              uint64_t *scratch, rr_totals *totals, hipStream_t stream);
-/* rr_rdbconvert.hip (include/rr_rdbconvert.h): flags, scan, compaction, sizes, scan, emit; scratch of
+/* rr_rdbconvert.hip (include/rr_rdbconvert.h): the attempted list, then the stage over it; scratch of
  * rr_rdbconvert_scratch_words(n).  opt6 as for rr_launch_rdbload */
 uint64_t rr_rdbconvert_scratch_words(uint64_t n);
 hipError_t rr_launch_rdbconvert(const uint8_t *data, uint64_t in_cap, const uint64_t *in_offs, const uint8_t *types,
@@ -104,14 +107,14 @@ hipError_t rr_launch_rdbconvert(const uint8_t *data, uint64_t in_cap, const uint
                                 uint64_t *out_offs, uint8_t *out_types, uint8_t *status, uint64_t *scratch, rr_totals *totals,
                                 hipStream_t stream);
 /* rr_rdbzset.hip (include/rr_d2string.h, include/rr_rdbzset.h).  The printer: one launch, none for n ==
- * 0.  The stage: flags, scan, compaction, sizes, scan, emit; scratch of rr_rdbzset_scratch_words(n);
+ * 0.  The stage: as rr_rdbconvert.hip's, the same scratch formula (rr_rdbzset_scratch_words(n));
  * opt6 as for rr_launch_rdbload */
 hipError_t rr_launch_d2string(const uint64_t *bits, uint64_t n, uint8_t *text, uint8_t *len, hipStream_t stream);
 uint64_t rr_rdbzset_scratch_words(uint64_t n);
 hipError_t rr_launch_rdbzset(const uint8_t *data, uint64_t in_cap, const uint64_t *in_offs, const uint8_t *types,
                              const uint8_t *convert_status, uint64_t n, const uint32_t *opt6, uint8_t *out, uint64_t out_cap,
                              uint64_t *out_offs, uint8_t *status, uint64_t *scratch, rr_totals *totals, hipStream_t stream);
-/* rr_aof.hip (include/rr_aof.h): sizes, scan, emit; scratch of rr_aof_scratch_words(n).  expires may
+/* rr_aof.hip (include/rr_aof.h): the stage; scratch of rr_aof_scratch_words(n).  expires may
  * be NULL; every other pointer on the device */
 uint64_t rr_aof_scratch_words(uint64_t n);
 hipError_t rr_launch_aof(const rr_value *values, const rr_elem *elems, uint64_t elem_cap, const uint8_t *arena,

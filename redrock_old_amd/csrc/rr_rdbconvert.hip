@@ -1,14 +1,11 @@
 // rr_rdbconvert.hip — gfx950 kernels of include/rr_rdbconvert.h: the values rr_rdbload_batch left
 // with RR_RDBLOAD_E_CONVERT, in the encoding rdbLoadObject picks for them (rdb.c:1476-1600): a Set of
-// integers as an intset, a small Hash and a small ZSet as ziplists.  Six launches:
-// rdbconvert_flag_kernel (a thread a value: which values are attempted, RR_RDBCONVERT_SKIP for the
-// rest, and the zeroing the other launches rely on), rr_launch_scan_u64, rdbconvert_compact_kernel
-// (the attempted values' indices, in order), rdbconvert_size_kernel (every decision and the blob
-// sizes), rr_launch_scan_u64, rdbconvert_emit_kernel (the bytes, RR_E_CAPACITY, the totals).
+// integers as an intset, a small Hash and a small ZSet as ziplists.  The stage is rr_stage_device.h's
+// with its attempted list in front (flags, scan, compaction, then size, scan, emit over the list):
+// rdbconvert_size_kernel takes every decision, rdbconvert_emit_kernel writes the bytes; at most
+// RR_RDBCONVERT_MAX_WAVES waves a launch.
 //
-// The attempted values are the rare class of a batch, so the size and emit passes run over the
-// compacted list, a wave per value, at most RR_RDBCONVERT_MAX_WAVES waves a launch and a grid stride
-// beyond.  The walk is rr_rdbload.hip's (rr_rdbload_device.h): wave-uniform, every load of payload
+// The walk is rr_rdbload.hip's (rr_rdbload_device.h): wave-uniform, every load of payload
 // bytes in the size pass through a buffer resource over exactly the value's slice, so a value that
 // is not what its load_status claims reads zeros, never a neighbour, and ends as E_CONVERT.
 //
@@ -174,37 +171,11 @@ __device__ uint64_t convert_value(Rd &r, uint32_t type, const Opt &O, const Lds 
     return size;
 }
 
-// att[i] = 1 for the attempted values (att[n] = 0), everything a value that is not converted keeps
-// (RR_RDBCONVERT_SKIP or E_CONVERT, size 0, type 0), and the zeroing the other launches rely on (both
-// scans' look-back and error words, the totals)
-__global__ __launch_bounds__(256) void rdbconvert_flag_kernel(const uint8_t *__restrict__ load_status, uint64_t n,
-                                                              uint64_t *__restrict__ att, uint64_t *__restrict__ out_offs,
-                                                              uint8_t *__restrict__ out_types, uint8_t *__restrict__ status,
-                                                              uint64_t *__restrict__ zero, uint64_t nzero, rr_totals *totals) {
-    const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
-    const uint64_t gtid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (uint64_t k = gtid; k < nzero; k += nthreads) zero[k] = 0;
-    if (gtid == 0) {
-        att[n] = 0;
-        out_offs[n] = 0;
-        totals->n_elems = totals->bytes = totals->n_bad = totals->payload = 0;
-    }
-    for (uint64_t i = gtid; i < n; i += nthreads) {
-        const bool a = load_status[i] == RR_RDBLOAD_E_CONVERT;
-        att[i] = a ? 1 : 0;
-        out_offs[i] = 0;
-        out_types[i] = 0;
-        status[i] = a ? RR_RDBLOAD_E_CONVERT : RR_RDBCONVERT_SKIP;
-    }
-}
-
-// att scanned: list[att[i]] = i for the attempted values
-__global__ __launch_bounds__(256) void rdbconvert_compact_kernel(const uint8_t *__restrict__ load_status, uint64_t n,
-                                                                 const uint64_t *__restrict__ att, uint32_t *__restrict__ list) {
-    const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += nthreads)
-        if (load_status[i] == RR_RDBLOAD_E_CONVERT) list[att[i]] = (uint32_t)i;
-}
+// attempted: what rr_rdbload_batch left with E_CONVERT
+struct ConvertAttempted {
+    const uint8_t *__restrict__ load_status;
+    __device__ __forceinline__ bool operator()(uint64_t i) const { return load_status[i] == RR_RDBLOAD_E_CONVERT; }
+};
 
 // blob sizes into out_offs[], status and out_types of the list's values (att[n] of them)
 __global__ __launch_bounds__(WPB * RR_WAVE) void rdbconvert_size_kernel(const uint8_t *__restrict__ data, uint64_t in_cap,
@@ -224,6 +195,7 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void rdbconvert_size_kernel(const ui
         const uint64_t o0 = first64(in_offs[v]), o1 = first64(in_offs[v + 1]);
         uint32_t st = RR_RDBLOAD_E_CONVERT, ot = 0;
         uint64_t size = 0, pay = 0, nel = 0;
+        // (slice_ok and rd_of written out: through the helpers this kernel's walk is scheduled differently, 76 bytes longer)
         if (o0 <= o1 && o1 <= in_cap && o1 - o0 < MAX_SLICE) {
             Rd r = {mk_rsrc(data + o0, (uint32_t)(o1 - o0)), data + o0, (uint32_t)(o1 - o0), 0};
             size = convert_value<false>(r, type, O, W, nullptr, st, ot, pay, nel);
@@ -264,56 +236,34 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void rdbconvert_emit_kernel(const ui
         }
         const uint32_t type = rfl(types[v]);
         const uint64_t o0 = first64(in_offs[v]), o1 = first64(in_offs[v + 1]);
-        Rd r = {mk_rsrc(data + o0, (uint32_t)(o1 - o0)), data + o0, (uint32_t)(o1 - o0), 0};
+        Rd r = rd_of(data, o0, o1);
         convert_value<true>(r, type, O, W, out + b0, st, ot, pay, nel);
     }
-    if (lane_id() == 0) {
-        if (pay) atomicAdd((unsigned long long *)&totals->payload, (unsigned long long)pay);
-        if (nel) atomicAdd((unsigned long long *)&totals->n_elems, (unsigned long long)nel);
-        if (n_bad) atomicAdd((unsigned long long *)&totals->n_bad, (unsigned long long)n_bad);
-    }
-}
-
-uint32_t wave_grid(uint64_t n) {   // a wave a value, capped
-    const uint64_t b = (n + WPB - 1) / WPB;
-    return (uint32_t)(b < GRID_CAP ? (b ? b : 1) : GRID_CAP);
-}
-uint32_t thread_grid(uint64_t n) {   // a thread a value, capped
-    const uint64_t b = (n + 255) / 256;
-    return (uint32_t)(b < 16384 ? (b ? b : 1) : 16384);
+    add_totals(totals, pay, nel, n_bad);
 }
 
 }  // namespace
 
-// scratch: two scans' look-back and error words, att[n + 1], list[n] (u32)
-extern "C" uint64_t rr_rdbconvert_scratch_words(uint64_t n) { return 2 * (rr_scan_words(n) + 1) + (n + 1) + (n + 1) / 2 + 1; }
+extern "C" uint64_t rr_rdbconvert_scratch_words(uint64_t n) { return AttScratch::words(n); }
 
 extern "C" hipError_t rr_launch_rdbconvert(const uint8_t *data, uint64_t in_cap, const uint64_t *in_offs, const uint8_t *types,
                                            const uint8_t *load_status, uint64_t n, const uint32_t *opt6, uint8_t *out,
                                            uint64_t out_cap, uint64_t *out_offs, uint8_t *out_types, uint8_t *status,
                                            uint64_t *scratch, rr_totals *totals, hipStream_t stream) {
-    const uint64_t lbw = rr_scan_words(n);
-    uint64_t *lb1 = scratch, *err1 = lb1 + lbw, *lb2 = err1 + 1, *err2 = lb2 + lbw, *att = err2 + 1;
-    uint32_t *list = (uint32_t *)(att + n + 1);
-    const Opt O = {opt6[0], opt6[1], opt6[2], opt6[3], opt6[4], opt6[5]};
-    hipLaunchKernelGGL(rdbconvert_flag_kernel, dim3(thread_grid(n)), dim3(256), 0, stream, load_status, n, att, out_offs, out_types,
-                       status, scratch, 2 * (lbw + 1), totals);
-    hipError_t e = hipGetLastError();
+    const AttScratch S(scratch, n);
+    const Opt O = opt_of(opt6);
+    const uint32_t grid = capped_grid(n, WPB, GRID_CAP);   // a wave a value
+    hipError_t e = launch_attempted(ConvertAttempted{load_status}, n, S, out_offs, out_types, status, RR_RDBLOAD_E_CONVERT,
+                                    RR_RDBCONVERT_SKIP, totals, stream);
     if (e != hipSuccess) return e;
-    e = rr_launch_scan_u64(att, n, lb1, err1, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(rdbconvert_compact_kernel, dim3(thread_grid(n)), dim3(256), 0, stream, load_status, n, (const uint64_t *)att,
-                       list);
+    hipLaunchKernelGGL(rdbconvert_size_kernel, dim3(grid), dim3(WPB * RR_WAVE), 0, stream, data, in_cap, in_offs, types, n,
+                       (const uint32_t *)S.list, (const uint64_t *)S.att, O, out_offs, out_types, status);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(rdbconvert_size_kernel, dim3(wave_grid(n)), dim3(WPB * RR_WAVE), 0, stream, data, in_cap, in_offs, types, n,
-                       (const uint32_t *)list, (const uint64_t *)att, O, out_offs, out_types, status);
-    e = hipGetLastError();
+    e = rr_launch_scan_u64(out_offs, n, S.lb2, S.err2, stream);
     if (e != hipSuccess) return e;
-    e = rr_launch_scan_u64(out_offs, n, lb2, err2, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(rdbconvert_emit_kernel, dim3(wave_grid(n)), dim3(WPB * RR_WAVE), 0, stream, data, in_offs, types, n,
-                       (const uint32_t *)list, (const uint64_t *)att, O, (const uint64_t *)out_offs, out, out_cap, status,
-                       (const uint64_t *)err1, (const uint64_t *)err2, totals);
+    hipLaunchKernelGGL(rdbconvert_emit_kernel, dim3(grid), dim3(WPB * RR_WAVE), 0, stream, data, in_offs, types, n,
+                       (const uint32_t *)S.list, (const uint64_t *)S.att, O, (const uint64_t *)out_offs, out, out_cap, status,
+                       (const uint64_t *)S.err1, (const uint64_t *)S.err2, totals);
     return hipGetLastError();
 }

@@ -20,13 +20,15 @@
 //   wave_crc: the same for one value's bytes by one wave (rdbdump_emit_kernel, rdbdump_check_kernel).
 //
 // The section.  file_size_kernel (a record a lane: status, size), rr_launch_scan_u64 over
-// head_bytes | sizes, file_emit_kernel (a record a lane for the header and for a key or payload of
-// up to SHORT_BODY bytes, the whole wave in turn for each longer one, 16 bytes a lane), then the two
-// CRC kernels over the assembled bytes.  A section that does not fit out_cap is not written at all.
+// head_bytes | sizes, file_emit_kernel (a record a lane for the header; the key and the payload are
+// copy_bodies'), then the two CRC kernels over the assembled bytes.  A section that does not fit
+// out_cap is not written at all.  The shape is rr_stage_device.h's, with loops of its own: a record
+// a lane, y[] one word ahead of the records (head_bytes in front), and the calls report through
+// rr_rdbfile_result, not rr_totals.  The leaves are the shared ones.
 #include <hip/hip_runtime.h>
 
 #include "rr_rdb_device.h"
-#include "rr_kernels.h"
+#include "rr_stage_device.h"
 #include "../../include/rr_rdbfile.h"
 
 using namespace rr;
@@ -38,8 +40,6 @@ constexpr uint32_t RUN = RR_CRC64_RUN, PIECE = RR_CRC64_PIECE;
 constexpr uint32_t MAX_WAVES = RR_CRC64_MAX_WAVES, PER_LANE = MAX_WAVES / RR_WAVE;
 constexpr uint32_t DUMP_GRID = RR_RDBDUMP_MAX_WAVES / WPB;
 constexpr uint32_t REC_GRID_CAP = 4096;           // workgroups of the section's size and emit kernels
-constexpr uint32_t SHORT_BODY = 32;               // a key or payload of up to this many bytes is copied by its own lane
-constexpr uint64_t MAX_SLICE = 0x7FFFFFF0ull;
 constexpr uint64_t POLY = 0x95ac9329ac4bc9b5ull;  // 0xad93d23594c935a9 reflected
 constexpr uint64_t ONE = 1ull << 63;              // x^0 in the reflected bit order
 static_assert(PIECE == RR_WAVE * RUN && MAX_WAVES % RR_WAVE == 0 && RUN % 8 == 0, "a lane a run");
@@ -232,29 +232,15 @@ struct Sec {
     uint32_t flags;
 };
 
-__device__ __forceinline__ bool slice_ok(uint64_t o0, uint64_t o1, uint64_t cap) { return o0 <= o1 && o1 <= cap && o1 - o0 < MAX_SLICE; }
-
-// a lane's body: by the lane itself when short, else by the whole wave, the lanes' bodies in turn
-__device__ __forceinline__ void copy_bodies(uint8_t *dst, const uint8_t *__restrict__ src, uint32_t len, bool mine) {
-    if (mine && len <= SHORT_BODY)
-        for (uint32_t k = 0; k < len; ++k) dst[k] = src[k];
-    wave_copy_each(dst, src, len, mine && len > SHORT_BODY);
-}
-
 // y[0] = head_bytes, y[1 + i] = record i's size, y[n + 1] = 0 (the scan's total); rec_status; and
-// the zeroing the later launches rely on (the scan's look-back words, the error word, the result)
+// the stage's zeroing
 __global__ __launch_bounds__(WPB * RR_WAVE) void file_size_kernel(Sec S, uint64_t *__restrict__ y, uint8_t *__restrict__ rec_status,
                                                                   uint64_t *__restrict__ zero, uint64_t nzero,
                                                                   rr_rdbfile_result *result) {
     const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
     const uint64_t gtid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (uint64_t k = gtid; k < nzero; k += nthreads) zero[k] = 0;
-    if (gtid == 0) {
-        y[0] = S.head_bytes;
-        y[S.n + 1] = 0;
-        result->bytes = result->n_bad = 0;
-        result->status = result->rsv = 0;
-    }
+    zero_stage_words(gtid, nthreads, zero, nzero, &y[S.n + 1], result);
+    if (gtid == 0) y[0] = S.head_bytes;
     for (uint64_t i = gtid; i < S.n; i += nthreads) {
         uint32_t st = RR_OK;
         uint64_t size = 0;
@@ -360,12 +346,7 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void dump_size_kernel(const uint64_t
                                                                   uint64_t *__restrict__ zero, uint64_t nzero, rr_rdbfile_result *result) {
     const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
     const uint64_t gtid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (uint64_t k = gtid; k < nzero; k += nthreads) zero[k] = 0;
-    if (gtid == 0) {
-        out_offs[n] = 0;
-        result->bytes = result->n_bad = 0;
-        result->status = result->rsv = 0;
-    }
+    zero_stage_words(gtid, nthreads, zero, nzero, &out_offs[n], result);
     for (uint64_t i = gtid; i < n; i += nthreads) {
         const uint64_t o0 = in_offs[i], o1 = in_offs[i + 1];
         const bool ok = status[i] == 0 && slice_ok(o0, o1, in_cap);
@@ -423,12 +404,7 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void dump_check_kernel(const uint8_t
     const uint32_t lane = lane_id();
     const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
     const uint64_t gtid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (uint64_t k = gtid; k < nzero; k += nthreads) zero[k] = 0;
-    if (gtid == 0) {
-        out_offs[n] = 0;
-        result->bytes = result->n_bad = 0;
-        result->status = result->rsv = 0;
-    }
+    zero_stage_words(gtid, nthreads, zero, nzero, &out_offs[n], result);
     const uint64_t nwaves = nthreads / RR_WAVE;
     for (uint64_t v = first64(gtid / RR_WAVE); v < n; v += nwaves) {
         const uint64_t o0 = first64(in_offs[v]), o1 = first64(in_offs[v + 1]);
@@ -480,12 +456,8 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void dump_unpack_kernel(const uint8_
     if (lane == 0 && n_bad) atomicAdd((unsigned long long *)&result->n_bad, (unsigned long long)n_bad);
 }
 
-uint32_t grid_for(uint64_t items_per_block, uint64_t n, uint32_t cap) {
-    const uint64_t b = (n + items_per_block - 1) / items_per_block;
-    return (uint32_t)(b < cap ? (b ? b : 1) : cap);
-}
 // the stream pass's workgroups for at most `bytes` bytes
-uint32_t crc_grid(uint64_t bytes) { return grid_for((uint64_t)WPB * PIECE, bytes, MAX_WAVES / WPB); }
+uint32_t crc_grid(uint64_t bytes) { return capped_grid(bytes, (uint64_t)WPB * PIECE, MAX_WAVES / WPB); }
 
 }  // namespace
 
@@ -515,7 +487,7 @@ extern "C" hipError_t rr_launch_rdbfile(const rr_rdbfile_in *in, uint32_t flags,
     uint64_t *y = scratch, *lb = y + n + 2, *err = lb + lbw, *part = err + 1;
     const Sec S = {in->payloads.data, in->payloads.offsets, in->payloads.data_cap, in->keys.data, in->keys.offsets, in->keys.data_cap,
                    in->types, in->status, in->expires, in->idle, in->freq, in->head, in->head_bytes, n, flags};
-    const uint32_t gs = grid_for(WPB * RR_WAVE, n, REC_GRID_CAP);
+    const uint32_t gs = capped_grid(n, WPB * RR_WAVE, REC_GRID_CAP);
     hipLaunchKernelGGL(file_size_kernel, dim3(gs), dim3(WPB * RR_WAVE), 0, stream, S, y, rec_status, lb, lbw + 1, result);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -543,13 +515,13 @@ extern "C" hipError_t rr_launch_rdbdump(const uint8_t *data, uint64_t in_cap, co
                                         uint8_t *out_status, uint64_t *scratch, rr_rdbfile_result *result, hipStream_t stream) {
     const uint64_t lbw = rr_scan_words(n);
     uint64_t *lb = scratch, *err = scratch + lbw;
-    hipLaunchKernelGGL(dump_size_kernel, dim3(grid_for(WPB * RR_WAVE, n, REC_GRID_CAP)), dim3(WPB * RR_WAVE), 0, stream, in_offs, in_cap,
+    hipLaunchKernelGGL(dump_size_kernel, dim3(capped_grid(n, WPB * RR_WAVE, REC_GRID_CAP)), dim3(WPB * RR_WAVE), 0, stream, in_offs, in_cap,
                        status, n, out_offs, out_status, lb, lbw + 1, result);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     e = rr_launch_scan_u64(out_offs, n, lb, err, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(dump_emit_kernel, dim3(grid_for(WPB, n, DUMP_GRID)), dim3(WPB * RR_WAVE), 0, stream, data, in_offs, types, n,
+    hipLaunchKernelGGL(dump_emit_kernel, dim3(capped_grid(n, WPB, DUMP_GRID)), dim3(WPB * RR_WAVE), 0, stream, data, in_offs, types, n,
                        (const uint64_t *)out_offs, out, out_cap, out_status, (const uint64_t *)err, result);
     return hipGetLastError();
 }
@@ -559,13 +531,13 @@ extern "C" hipError_t rr_launch_rdbdump_verify(const uint8_t *data, uint64_t in_
                                                rr_rdbfile_result *result, hipStream_t stream) {
     const uint64_t lbw = rr_scan_words(n);
     uint64_t *lb = scratch, *err = scratch + lbw;
-    hipLaunchKernelGGL(dump_check_kernel, dim3(grid_for(WPB, n, DUMP_GRID)), dim3(WPB * RR_WAVE), 0, stream, data, in_cap, in_offs, n,
+    hipLaunchKernelGGL(dump_check_kernel, dim3(capped_grid(n, WPB, DUMP_GRID)), dim3(WPB * RR_WAVE), 0, stream, data, in_cap, in_offs, n,
                        out_offs, types, status, lb, lbw + 1, result);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     e = rr_launch_scan_u64(out_offs, n, lb, err, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(dump_unpack_kernel, dim3(grid_for(WPB, n, DUMP_GRID)), dim3(WPB * RR_WAVE), 0, stream, data, in_offs, n,
+    hipLaunchKernelGGL(dump_unpack_kernel, dim3(capped_grid(n, WPB, DUMP_GRID)), dim3(WPB * RR_WAVE), 0, stream, data, in_offs, n,
                        (const uint64_t *)out_offs, out, out_cap, status, (const uint64_t *)err, result);
     return hipGetLastError();
 }

@@ -1,10 +1,9 @@
 // rr_rdbload.hip — gfx950 kernels of include/rr_rdbload.h: RDB value payloads -> rock blobs (the
-// blob desObject turns into the object rdbLoadObject builds, rdb.c:1450-1700).  Three launches:
-// rdbload_size_kernel (every decision: status, CONVERT, an LZF stream's validity and exact output
-// length; blob sizes into out_offsets[]), rr_launch_scan_u64, rdbload_emit_kernel (the bytes of the
-// values that are valid and fit, RR_E_CAPACITY for those that do not, the call's totals).
+// blob desObject turns into the object rdbLoadObject builds, rdb.c:1450-1700).  The stage is
+// rr_stage_device.h's (size, scan, emit): rdbload_size_kernel takes every decision (status, CONVERT,
+// an LZF stream's validity and exact output length), rdbload_emit_kernel writes the bytes.
 //
-// A wave per value, values strided over a capped grid.  A value is a chain of dependent length
+// A value is a chain of dependent length
 // prefixes, so the walk is wave-uniform: every lane takes the same path, the state lives in scalar
 // registers, and the lanes are used where bytes are independent.  A header is read by one 64-byte
 // load, a byte a lane, and picked apart with readlane (one memory round trip per string, per
@@ -270,8 +269,7 @@ __device__ __forceinline__ lds_u8 *wave_window() {
     return (lds_u8 *)windows + (threadIdx.x / RR_WAVE) * WIN;
 }
 
-// blob sizes into out_offs[0, n), out_offs[n] = 0; status; and the zeroing the other two launches
-// rely on (the scan's look-back words, the error word, totals)
+// blob sizes into out_offs[0, n), out_offs[n] = 0; status; and the stage's zeroing
 __global__ __launch_bounds__(WPB * RR_WAVE) void rdbload_size_kernel(const uint8_t *__restrict__ data, uint64_t in_cap,
                                                                      const uint64_t *__restrict__ in_offs,
                                                                      const uint8_t *__restrict__ types, uint64_t n, Opt O,
@@ -280,11 +278,7 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void rdbload_size_kernel(const uint8
     lds_u8 *win = wave_window();
     const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
     const uint64_t gtid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (uint64_t k = gtid; k < nzero; k += nthreads) zero[k] = 0;
-    if (gtid == 0) {
-        out_offs[n] = 0;
-        totals->n_elems = totals->bytes = totals->n_bad = totals->payload = 0;
-    }
+    zero_stage_words(gtid, nthreads, zero, nzero, &out_offs[n], totals);
     const uint64_t nwaves = nthreads / RR_WAVE;
     for (uint64_t v = first64(gtid / RR_WAVE); v < n; v += nwaves) {
         const uint32_t type = rfl(types[v]);
@@ -295,7 +289,7 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void rdbload_size_kernel(const uint8
         else if (o0 > o1 || o1 > in_cap) st = RR_RDBLOAD_E_TRUNC;
         else if (o1 - o0 >= MAX_SLICE) st = RR_RDBLOAD_E_LEN;
         else {
-            Rd r = {mk_rsrc(data + o0, (uint32_t)(o1 - o0)), data + o0, (uint32_t)(o1 - o0), 0};
+            Rd r = rd_of(data, o0, o1);
             size = load_value<false>(r, type, O, win, nullptr, st, pay, nel);
         }
         if (lane_id() == 0) {
@@ -329,19 +323,10 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void rdbload_emit_kernel(const uint8
             continue;
         }
         const uint64_t o0 = first64(in_offs[v]), o1 = first64(in_offs[v + 1]);
-        Rd r = {mk_rsrc(data + o0, (uint32_t)(o1 - o0)), data + o0, (uint32_t)(o1 - o0), 0};
+        Rd r = rd_of(data, o0, o1);
         load_value<true>(r, type, O, win, out + b0, st, pay, nel);
     }
-    if (lane_id() == 0) {
-        if (pay) atomicAdd((unsigned long long *)&totals->payload, (unsigned long long)pay);
-        if (nel) atomicAdd((unsigned long long *)&totals->n_elems, (unsigned long long)nel);
-        if (n_bad) atomicAdd((unsigned long long *)&totals->n_bad, (unsigned long long)n_bad);
-    }
-}
-
-uint32_t grid_for(uint64_t n) {
-    const uint64_t b = (n + WPB - 1) / WPB;
-    return (uint32_t)(b < GRID_CAP ? (b ? b : 1) : GRID_CAP);
+    add_totals(totals, pay, nel, n_bad);
 }
 
 }  // namespace
@@ -354,14 +339,15 @@ extern "C" hipError_t rr_launch_rdbload(const uint8_t *data, uint64_t in_cap, co
                                         uint8_t *status, uint64_t *scratch, rr_totals *totals, hipStream_t stream) {
     const uint64_t lbw = rr_scan_words(n);
     uint64_t *lb = scratch, *err = scratch + lbw;
-    const Opt O = {opt6[0], opt6[1], opt6[2], opt6[3], opt6[4], opt6[5]};
-    hipLaunchKernelGGL(rdbload_size_kernel, dim3(grid_for(n)), dim3(WPB * RR_WAVE), 0, stream, data, in_cap, in_offs, types, n, O,
+    const Opt O = opt_of(opt6);
+    const uint32_t grid = capped_grid(n, WPB, GRID_CAP);
+    hipLaunchKernelGGL(rdbload_size_kernel, dim3(grid), dim3(WPB * RR_WAVE), 0, stream, data, in_cap, in_offs, types, n, O,
                        out_offs, status, lb, lbw + 1, totals);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     e = rr_launch_scan_u64(out_offs, n, lb, err, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(rdbload_emit_kernel, dim3(grid_for(n)), dim3(WPB * RR_WAVE), 0, stream, data, in_offs, types, n, O,
+    hipLaunchKernelGGL(rdbload_emit_kernel, dim3(grid), dim3(WPB * RR_WAVE), 0, stream, data, in_offs, types, n, O,
                        (const uint64_t *)out_offs, out, out_cap, status, (const uint64_t *)err, totals);
     return hipGetLastError();
 }

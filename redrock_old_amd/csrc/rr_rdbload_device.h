@@ -8,17 +8,18 @@
 // string's head: src_peek at k == 0 and materialize with need <= 64 touch the first 64 bytes only.
 #pragma once
 #include "rr_rdb_device.h"
+#include "rr_stage_device.h"
 #include "../../include/rr_rdbload.h"
 
 namespace rr {
 
 constexpr uint32_t WIN = RR_RDBLOAD_LZF_NODE_MAX;   // a wave's LDS window, bytes
-constexpr uint32_t MAX_SLICE = 0x7FFFFFF0u;         // a buffer resource's reach
 
 // rr_rdbload_opts as the kernels take it: lru & RR_LRU_MASK, then the five thresholds
 struct Opt {
     uint32_t lru, set_ie, hash_e, hash_v, zset_e, zset_v;
 };
+inline Opt opt_of(const uint32_t *opt6) { return {opt6[0], opt6[1], opt6[2], opt6[3], opt6[4], opt6[5]}; }
 
 // little- and big-endian numbers out of a peeked register: byte i of the number is lane at + i
 __device__ __forceinline__ uint64_t le_lanes(uint32_t v, uint32_t at, uint32_t nb) {
@@ -37,6 +38,10 @@ struct Rd {
     const uint8_t *base;    // its first byte (raw pointer: used for ranges the size pass has checked)
     uint32_t n, p;          // its length, the read position
 };
+// the reader at the start of the slice [o0, o1) of data (slice_ok)
+__device__ __forceinline__ Rd rd_of(const uint8_t *data, uint64_t o0, uint64_t o1) {
+    return {mk_rsrc(data + o0, (uint32_t)(o1 - o0)), data + o0, (uint32_t)(o1 - o0), 0};
+}
 // a string as rdbGenericLoadStringObject meets it (rdb.c:487-540)
 enum : uint32_t { S_RAW = 0, S_INT = 1, S_LZF = 2 };
 struct Str {

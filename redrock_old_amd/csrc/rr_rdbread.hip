@@ -3,12 +3,13 @@
 // hands on for each key: the prefix opcodes' values, the type, the key's bytes and the value's
 // payload in rr_rdbload_batch's input shape; and the verdict on the stream's checksum (:2298-2311).
 //
-// Three launches: split_size_kernel (every decision: the status, the key's loaded length, which for
-// an LZF key means walking its stream, the payload's length), one rr_launch_scan_u64 over
-// key sizes | payload sizes in the call's scratch, split_emit_kernel (both offsets arrays, the keys
-// and the payloads of the records that are valid and fit).
+// The shape is rr_stage_device.h's (size, scan, emit), with loops of its own: a record has two
+// outputs, so one scan runs over key sizes | payload sizes in the call's scratch, the emit kernel
+// writes both offsets arrays, and the call reports through rr_rdbfile_result.  split_size_kernel takes
+// every decision (the status, the key's loaded length, which for an LZF key means walking its stream,
+// the payload's length); split_emit_kernel writes the keys and payloads that are valid and fit.
 //
-// A wave a record, records strided over a capped grid.  The key is read by the reader the RDB load
+// The key is read by the reader the RDB load
 // kernels share (rr_rdbload_device.h: parse_len, rd_string, emit_string, the LZF routines), and that
 // reader is wave-uniform: a header is one 64-byte load, a byte a lane, picked apart with readlane,
 // the state lives in scalar registers, and the lanes copy.  The prefix opcodes are read the same way,
@@ -84,10 +85,8 @@ __device__ __forceinline__ uint32_t rd_prefix(Rd &r, Pre &P) {
     }
 }
 
-__device__ __forceinline__ bool slice_ok(uint64_t s, uint64_t e, uint64_t cap) { return s <= e && e <= cap && e - s < MAX_SLICE; }
-
 // y[0, n) the keys' sizes, y[n, 2n) the payloads', y[2n] = 0 (the scan's total); the per-record arrays;
-// and the zeroing the later launches rely on (the scan's look-back words, the error word, the result)
+// and the stage's zeroing
 __global__ __launch_bounds__(WPB * RR_WAVE) void split_size_kernel(const uint8_t *__restrict__ data, uint64_t data_cap,
                                                                    const uint64_t *__restrict__ rec_start,
                                                                    const uint64_t *__restrict__ rec_end, uint64_t n,
@@ -96,12 +95,7 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void split_size_kernel(const uint8_t
                                                                    rr_rdbfile_result *result) {
     const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
     const uint64_t gtid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (uint64_t k = gtid; k < nzero; k += nthreads) zero[k] = 0;
-    if (gtid == 0) {
-        y[2 * n] = 0;
-        result->bytes = result->n_bad = 0;
-        result->status = result->rsv = 0;
-    }
+    zero_stage_words(gtid, nthreads, zero, nzero, &y[2 * n], result);
     const uint64_t nwaves = nthreads / RR_WAVE;
     for (uint64_t v = first64(gtid / RR_WAVE); v < n; v += nwaves) {
         const uint64_t s = first64(rec_start[v]), e = first64(rec_end[v]);
@@ -109,7 +103,7 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void split_size_kernel(const uint8_t
         uint64_t ksize = 0, psize = 0;
         Pre P = no_pre();
         if (slice_ok(s, e, data_cap)) {
-            Rd r = {mk_rsrc(data + s, (uint32_t)(e - s)), data + s, (uint32_t)(e - s), 0};
+            Rd r = rd_of(data, s, e);
             st = rd_prefix(r, P);
             if (!st) {
                 Str k;
@@ -167,7 +161,7 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void split_emit_kernel(const uint8_t
             continue;
         }
         const uint64_t s = first64(rec_start[v]), e = first64(rec_end[v]);
-        Rd r = {mk_rsrc(data + s, (uint32_t)(e - s)), data + s, (uint32_t)(e - s), 0};
+        Rd r = rd_of(data, s, e);
         Pre P;
         Str k;
         rd_prefix(r, P);
@@ -193,11 +187,6 @@ __global__ __launch_bounds__(RR_WAVE) void verdict_kernel(const uint8_t *__restr
     }
 }
 
-uint32_t grid_for(uint64_t n) {
-    const uint64_t b = (n + WPB - 1) / WPB;
-    return (uint32_t)(b < GRID_CAP ? (b ? b : 1) : GRID_CAP);
-}
-
 }  // namespace
 
 // scratch: y[2n + 1] | the scan's look-back words | the error word
@@ -208,13 +197,14 @@ extern "C" hipError_t rr_launch_rdbread_split(const uint8_t *data, uint64_t data
                                               rr_rdbfile_result *result, hipStream_t stream) {
     const uint64_t lbw = rr_scan_words(2 * n);
     uint64_t *y = scratch, *lb = y + 2 * n + 1, *err = lb + lbw;
-    hipLaunchKernelGGL(split_size_kernel, dim3(grid_for(n)), dim3(WPB * RR_WAVE), 0, stream, data, data_cap, rec_start, rec_end, n, y,
+    const uint32_t grid = capped_grid(n, WPB, GRID_CAP);   // a wave a record
+    hipLaunchKernelGGL(split_size_kernel, dim3(grid), dim3(WPB * RR_WAVE), 0, stream, data, data_cap, rec_start, rec_end, n, y,
                        *out, lb, lbw + 1, result);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     e = rr_launch_scan_u64(y, 2 * n, lb, err, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(split_emit_kernel, dim3(grid_for(n)), dim3(WPB * RR_WAVE), 0, stream, data, rec_start, rec_end, n,
+    hipLaunchKernelGGL(split_emit_kernel, dim3(grid), dim3(WPB * RR_WAVE), 0, stream, data, rec_start, rec_end, n,
                        (const uint64_t *)y, *out, (const uint64_t *)err, result);
     return hipGetLastError();
 }

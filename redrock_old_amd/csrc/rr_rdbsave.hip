@@ -3,10 +3,14 @@
 // offsets[], per-value status, a List's node count), rr_launch_scan_u64, rdb_emit_kernel (every type
 // but the List), rdb_list_kernel<1> and <2> (the Lists, and the call's accounting).
 //
-// A wave per value in the size and emit kernels, values strided over a capped grid.  A value's descriptors are
+// The stage's shape is rr_stage_device.h's (size, scan, emit), with loops of its own: a value's index
+// is not made wave-uniform here, the Lists have launches of their own, and the size and emit kernels
+// come in an LZF instantiation each.  The leaves (the zeroing, scan_costs, sum_lanes, copy_bodies,
+// value_ok, the grid) are the shared ones.
+//
+// A wave per value in the size and emit kernels.  A value's descriptors are
 // taken 64 a round, one a lane: every lane works out what its descriptor becomes and how many
-// bytes it costs, a wave scan places it, the lane writes its header and a body of up to 32 bytes,
-// and longer bodies are copied by the whole wave, 16 bytes a lane.
+// bytes it costs, a wave scan places it, the lane writes its header, and the bodies are copy_bodies'.
 //
 // A List is the serial part: whether an entry joins the tail node depends on the node's size so
 // far (_quicklistNodeAllowInsert, quicklist.c:420-450), its prevlen field on the entry before it,
@@ -20,7 +24,7 @@
 
 #include "rr_flat_device.h"
 #include "rr_rdb_device.h"
-#include "rr_kernels.h"
+#include "rr_stage_device.h"
 
 using namespace rr;
 
@@ -29,22 +33,6 @@ namespace {
 constexpr uint32_t WPB = 4;             // waves (values in flight) per workgroup
 constexpr uint32_t GRID_CAP = 16384;    // workgroups: 65536 waves, 256 per CU on 256 CUs (8 rounds of 32 resident)
 constexpr uint32_t LIST_GROUP = 8;      // values a wave of rdb_list_kernel looks at per step
-constexpr uint32_t SHORT_BODY = 32;     // a body of up to this many bytes is copied by its own lane
-
-// Wave64 inclusive scan of costs below 2^40 (a cost is at most 2^32 + 8), every lane active: the low
-// 24 bits and the rest scanned apart by the u32 DPP scan, which needs no per-step lane predicates
-// (the u64 shuffle scan keeps six of them in SGPR pairs, and they spilled here).
-__device__ __forceinline__ uint64_t scan_costs(uint64_t x) {
-    const uint32_t lo = wave_incl_scan_u32((uint32_t)x & 0xFFFFFFu), hi = wave_incl_scan_u32((uint32_t)(x >> 24));
-    return ((uint64_t)hi << 24) + lo;
-}
-
-// the sum of every lane's x (all lanes active), in three 24-bit pieces by the same scan
-__device__ __forceinline__ uint64_t sum_lanes(uint64_t x) {
-    const uint32_t a = wave_incl_scan_u32((uint32_t)x & 0xFFFFFFu), b = wave_incl_scan_u32((uint32_t)(x >> 24) & 0xFFFFFFu),
-                   c = wave_incl_scan_u32((uint32_t)(x >> 48));
-    return (uint64_t)rl32(a, RR_WAVE - 1) + ((uint64_t)rl32(b, RR_WAVE - 1) << 24) + ((uint64_t)rl32(c, RR_WAVE - 1) << 48);
-}
 
 // the size estimate _quicklistNodeAllowInsert adds for a pushed string of sz bytes (quicklist.c:425-441)
 __device__ __forceinline__ uint64_t ql_estimate(uint64_t sz) {
@@ -342,11 +330,9 @@ __device__ uint64_t save_plain(const Batch &B, LzfCtx &X, uint32_t type, uint32_
                 dbody = d + put_len(d, e.len);
             } else {
                 dbody = d + put_len(d, e.len);
-                if (e.len <= SHORT_BODY)
-                    for (uint32_t k = 0; k < e.len; ++k) dbody[k] = B.arena[e.data + k];
             }
         }
-        if (EMIT) wave_copy_each(dbody, B.arena + e.data, e.len, active && form == 0 && e.len > SHORT_BODY);
+        if (EMIT) copy_bodies(dbody, B.arena + e.data, e.len, active && form == 0);
         if (EMIT && LZF) {
             uint64_t m = __ballot(active && form == 4);
             while (m) {
@@ -467,11 +453,9 @@ __device__ uint64_t save_list(const Batch &B, uint32_t eb, uint32_t n, uint8_t *
                     if (e.len <= 0x3F) *d++ = (uint8_t)e.len;
                     else if (e.len <= 0x3FFF) { *d++ = (uint8_t)(0x40 | (e.len >> 8)); *d++ = (uint8_t)e.len; }
                     else { *d++ = 0x80; put_be(d, e.len, 4); d += 4; }
-                    if (e.len <= SHORT_BODY)
-                        for (uint32_t k = 0; k < e.len; ++k) d[k] = B.arena[e.data + k];
                 }
             }
-            wave_copy_each(d, B.arena + e.data, e.len, active && !isint && e.len > SHORT_BODY);
+            copy_bodies(d, B.arena + e.data, e.len, active && !isint);
         }
     }
     if (open) close_node();
@@ -493,13 +477,8 @@ __device__ __forceinline__ LzfCtx lzf_ctx(uint32_t *clens) {
     return X;
 }
 
-__device__ __forceinline__ bool value_ok(const uint4 &x, uint64_t elem_cap) {
-    const uint32_t vstatus = (x.x >> 16) & 0xFFFF;
-    return vstatus == RR_OK && (uint64_t)x.w + (uint64_t)x.z <= elem_cap;
-}
-
 // sizes into offsets[0, n), offsets[n] = 0; status 0 / RR_E_ENCODE; types; a List's node count;
-// and the zeroing the other two launches rely on (the scan's look-back words, the error word, totals).
+// and the stage's zeroing.
 // LZF: also the stream length of every eligible string, into clens.
 template <bool LZF>
 __global__ __launch_bounds__(WPB * RR_WAVE) void rdb_size_kernel(const rr_value *__restrict__ values, uint64_t n, Batch B,
@@ -510,11 +489,7 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void rdb_size_kernel(const rr_value 
     LzfCtx X = lzf_ctx<LZF>(clens);
     const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
     const uint64_t gtid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (uint64_t k = gtid; k < nzero; k += nthreads) zero[k] = 0;
-    if (gtid == 0) {
-        offsets[n] = 0;
-        totals->n_elems = totals->bytes = totals->n_bad = totals->payload = 0;
-    }
+    zero_stage_words(gtid, nthreads, zero, nzero, &offsets[n], totals);
     const uint64_t nwaves = nthreads / RR_WAVE;
     uint64_t pay = 0;
     for (uint64_t v = gtid / RR_WAVE; v < n; v += nwaves) {
@@ -557,8 +532,7 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void rdb_emit_kernel(const rr_value 
         if (o1 == o0 || o1 > data_cap || type == RR_TYPE_LIST_QUICKLIST) continue;   // unsaveable / does not fit / a List
         save_plain<true, LZF>(B, X, type, enc, x.w, x.z, out + o0, pay);
     }
-    pay = sum_lanes(pay);
-    if (lane_id() == 0 && pay) atomicAdd((unsigned long long *)&totals->payload, (unsigned long long)pay);
+    add_totals(totals, sum_lanes(pay), 0, 0);
 }
 
 // The Lists that the emit kernel left out, in two launches: MODE 1 parks every node's final size at
@@ -609,14 +583,8 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void rdb_list_kernel(const rr_value 
         if (lane == 0 && n_bad) atomicAdd((unsigned long long *)&totals->n_bad, (unsigned long long)n_bad);
         if (lane == 0 && n_el) atomicAdd((unsigned long long *)&totals->n_elems, (unsigned long long)n_el);
     } else {
-        pay = sum_lanes(pay);
-        if (lane == 0 && pay) atomicAdd((unsigned long long *)&totals->payload, (unsigned long long)pay);
+        add_totals(totals, sum_lanes(pay), 0, 0);
     }
-}
-
-uint32_t grid_for(uint64_t n) {
-    const uint64_t b = (n + WPB - 1) / WPB;
-    return (uint32_t)(b < GRID_CAP ? (b ? b : 1) : GRID_CAP);
 }
 
 }  // namespace
@@ -636,17 +604,18 @@ extern "C" hipError_t rr_launch_rdbsave(const rr_value *values, const rr_elem *e
     uint32_t *nnodes = reinterpret_cast<uint32_t *>(err + 1);
     uint32_t *clens = lzf ? reinterpret_cast<uint32_t *>(err + 1 + (n + 1) / 2 + 1) : nullptr;
     const Batch B = {elems, elem_cap, arena, arena_cap, list_fill};
-    hipLaunchKernelGGL(lzf ? rdb_size_kernel<true> : rdb_size_kernel<false>, dim3(grid_for(n)), dim3(WPB * RR_WAVE), 0, stream,
+    const uint32_t grid = capped_grid(n, WPB, GRID_CAP);   // a wave a value
+    hipLaunchKernelGGL(lzf ? rdb_size_kernel<true> : rdb_size_kernel<false>, dim3(grid), dim3(WPB * RR_WAVE), 0, stream,
                        values, n, B, offsets, types, status, nnodes, lb, lbw + 1, totals, clens);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     e = rr_launch_scan_u64(offsets, n, lb, err, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(lzf ? rdb_emit_kernel<true> : rdb_emit_kernel<false>, dim3(grid_for(n)), dim3(WPB * RR_WAVE), 0, stream,
+    hipLaunchKernelGGL(lzf ? rdb_emit_kernel<true> : rdb_emit_kernel<false>, dim3(grid), dim3(WPB * RR_WAVE), 0, stream,
                        values, n, B, (const uint64_t *)offsets, out, cap, totals, clens);
     e = hipGetLastError();
     if (e != hipSuccess || n == 0) return e;
-    const uint32_t lgrid = grid_for((n + LIST_GROUP - 1) / LIST_GROUP);
+    const uint32_t lgrid = capped_grid(n, WPB * LIST_GROUP, GRID_CAP);
     hipLaunchKernelGGL(rdb_list_kernel<1>, dim3(lgrid), dim3(WPB * RR_WAVE), 0, stream, values, n, B, (const uint64_t *)offsets, out,
                        cap, (const uint32_t *)nnodes, status, (const uint64_t *)err, totals);
     hipLaunchKernelGGL(rdb_list_kernel<2>, dim3(lgrid), dim3(WPB * RR_WAVE), 0, stream, values, n, B, (const uint64_t *)offsets, out,

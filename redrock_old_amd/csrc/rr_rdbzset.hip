@@ -8,10 +8,8 @@
 // last byte).  d2string_kernel prints 64 scores a wave and copies the slots' written bytes out, 64
 // consecutive bytes an instruction.
 //
-// The stage has rr_rdbconvert.hip's shape, launch for launch: rdbzset_flag_kernel, rr_launch_scan_u64,
-// rdbzset_compact_kernel, rdbzset_size_kernel, rr_launch_scan_u64, rdbzset_emit_kernel, the last two
-// kernels a wave per attempted value.  Reading the payload and the rank sort are
-// rr_rdbconvert_device.h's.  Then, 64 ranks at a time, the lanes print the 64 scores into the slots
+// The stage is rr_stage_device.h's with its attempted list in front, as rr_rdbconvert.hip's.  Reading
+// the payload and the rank sort are rr_rdbconvert_device.h's.  Then, 64 ranks at a time, the lanes print the 64 scores into the slots
 // and the wave pushes member, text, member, text ... from them: the text through string2ll like any
 // string (zipTryEncoding), so "17" and "4503599627370496" are integer entries and "1.5" is not.
 //
@@ -147,40 +145,13 @@ __device__ uint64_t zset_value(Rd &r, const Opt &O, const ZLds &Z, uint8_t *out,
     return 13 + total;
 }
 
-__device__ __forceinline__ bool attempted(const uint8_t *types, const uint8_t *convert_status, uint64_t i) {
-    return convert_status[i] == RR_RDBLOAD_E_CONVERT && types[i] == RR_TYPE_ZSET_SKIPLIST;
-}
-
-// att[i] = 1 for the attempted values (att[n] = 0), the status and size of every value that is not
-// converted, and the zeroing the other launches rely on (both scans' look-back and error words, the totals)
-__global__ __launch_bounds__(256) void rdbzset_flag_kernel(const uint8_t *__restrict__ types, const uint8_t *__restrict__ convert_status,
-                                                           uint64_t n, uint64_t *__restrict__ att, uint64_t *__restrict__ out_offs,
-                                                           uint8_t *__restrict__ status, uint64_t *__restrict__ zero, uint64_t nzero,
-                                                           rr_totals *totals) {
-    const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
-    const uint64_t gtid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (uint64_t k = gtid; k < nzero; k += nthreads) zero[k] = 0;
-    if (gtid == 0) {
-        att[n] = 0;
-        out_offs[n] = 0;
-        totals->n_elems = totals->bytes = totals->n_bad = totals->payload = 0;
+// attempted: the ZSet_2 values rr_rdbconvert_batch left with E_CONVERT
+struct ZsetAttempted {
+    const uint8_t *__restrict__ types, *__restrict__ convert_status;
+    __device__ __forceinline__ bool operator()(uint64_t i) const {
+        return convert_status[i] == RR_RDBLOAD_E_CONVERT && types[i] == RR_TYPE_ZSET_SKIPLIST;
     }
-    for (uint64_t i = gtid; i < n; i += nthreads) {
-        const bool a = attempted(types, convert_status, i);
-        att[i] = a ? 1 : 0;
-        out_offs[i] = 0;
-        status[i] = a ? RR_RDBLOAD_E_CONVERT : RR_RDBZSET_SKIP;
-    }
-}
-
-// att scanned: list[att[i]] = i for the attempted values
-__global__ __launch_bounds__(256) void rdbzset_compact_kernel(const uint8_t *__restrict__ types,
-                                                              const uint8_t *__restrict__ convert_status, uint64_t n,
-                                                              const uint64_t *__restrict__ att, uint32_t *__restrict__ list) {
-    const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += nthreads)
-        if (attempted(types, convert_status, i)) list[att[i]] = (uint32_t)i;
-}
+};
 
 // blob sizes into out_offs[] and status of the list's values (att[n] of them)
 __global__ __launch_bounds__(WPB * RR_WAVE) void rdbzset_size_kernel(const uint8_t *__restrict__ data, uint64_t in_cap,
@@ -196,8 +167,8 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void rdbzset_size_kernel(const uint8
         const uint64_t o0 = first64(in_offs[v]), o1 = first64(in_offs[v + 1]);
         uint32_t st = RR_RDBLOAD_E_CONVERT;
         uint64_t size = 0, pay = 0, nel = 0;
-        if (o0 <= o1 && o1 <= in_cap && o1 - o0 < MAX_SLICE) {
-            Rd r = {mk_rsrc(data + o0, (uint32_t)(o1 - o0)), data + o0, (uint32_t)(o1 - o0), 0};
+        if (slice_ok(o0, o1, in_cap)) {
+            Rd r = rd_of(data, o0, o1);
             size = zset_value<false>(r, O, Z, nullptr, st, pay, nel);
         }
         if (lane_id() == 0 && st == RR_OK) {
@@ -232,23 +203,10 @@ __global__ __launch_bounds__(WPB * RR_WAVE) void rdbzset_emit_kernel(const uint8
             continue;
         }
         const uint64_t o0 = first64(in_offs[v]), o1 = first64(in_offs[v + 1]);
-        Rd r = {mk_rsrc(data + o0, (uint32_t)(o1 - o0)), data + o0, (uint32_t)(o1 - o0), 0};
+        Rd r = rd_of(data, o0, o1);
         zset_value<true>(r, O, Z, out + b0, st, pay, nel);
     }
-    if (lane_id() == 0) {
-        if (pay) atomicAdd((unsigned long long *)&totals->payload, (unsigned long long)pay);
-        if (nel) atomicAdd((unsigned long long *)&totals->n_elems, (unsigned long long)nel);
-        if (n_bad) atomicAdd((unsigned long long *)&totals->n_bad, (unsigned long long)n_bad);
-    }
-}
-
-uint32_t wave_grid(uint64_t n) {   // a wave a value, capped
-    const uint64_t b = (n + WPB - 1) / WPB;
-    return (uint32_t)(b < GRID_CAP ? (b ? b : 1) : GRID_CAP);
-}
-uint32_t thread_grid(uint64_t n) {   // a thread a value, capped
-    const uint64_t b = (n + 255) / 256;
-    return (uint32_t)(b < 16384 ? (b ? b : 1) : 16384);
+    add_totals(totals, pay, nel, n_bad);
 }
 
 }  // namespace
@@ -260,35 +218,26 @@ extern "C" hipError_t rr_launch_d2string(const uint64_t *bits, uint64_t n, uint8
     return hipGetLastError();
 }
 
-// scratch: two scans' look-back and error words, att[n + 1], list[n] (u32)
-extern "C" uint64_t rr_rdbzset_scratch_words(uint64_t n) { return 2 * (rr_scan_words(n) + 1) + (n + 1) + (n + 1) / 2 + 1; }
+extern "C" uint64_t rr_rdbzset_scratch_words(uint64_t n) { return AttScratch::words(n); }
 
 extern "C" hipError_t rr_launch_rdbzset(const uint8_t *data, uint64_t in_cap, const uint64_t *in_offs, const uint8_t *types,
                                         const uint8_t *convert_status, uint64_t n, const uint32_t *opt6, uint8_t *out,
                                         uint64_t out_cap, uint64_t *out_offs, uint8_t *status, uint64_t *scratch, rr_totals *totals,
                                         hipStream_t stream) {
-    const uint64_t lbw = rr_scan_words(n);
-    uint64_t *lb1 = scratch, *err1 = lb1 + lbw, *lb2 = err1 + 1, *err2 = lb2 + lbw, *att = err2 + 1;
-    uint32_t *list = (uint32_t *)(att + n + 1);
-    const Opt O = {opt6[0], opt6[1], opt6[2], opt6[3], opt6[4], opt6[5]};
-    hipLaunchKernelGGL(rdbzset_flag_kernel, dim3(thread_grid(n)), dim3(256), 0, stream, types, convert_status, n, att, out_offs, status,
-                       scratch, 2 * (lbw + 1), totals);
-    hipError_t e = hipGetLastError();
+    const AttScratch S(scratch, n);
+    const Opt O = opt_of(opt6);
+    const uint32_t grid = capped_grid(n, WPB, GRID_CAP);   // a wave a value
+    hipError_t e = launch_attempted(ZsetAttempted{types, convert_status}, n, S, out_offs, nullptr, status, RR_RDBLOAD_E_CONVERT,
+                                    RR_RDBZSET_SKIP, totals, stream);
     if (e != hipSuccess) return e;
-    e = rr_launch_scan_u64(att, n, lb1, err1, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(rdbzset_compact_kernel, dim3(thread_grid(n)), dim3(256), 0, stream, types, convert_status, n,
-                       (const uint64_t *)att, list);
+    hipLaunchKernelGGL(rdbzset_size_kernel, dim3(grid), dim3(WPB * RR_WAVE), 0, stream, data, in_cap, in_offs, n,
+                       (const uint32_t *)S.list, (const uint64_t *)S.att, O, out_offs, status);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(rdbzset_size_kernel, dim3(wave_grid(n)), dim3(WPB * RR_WAVE), 0, stream, data, in_cap, in_offs, n,
-                       (const uint32_t *)list, (const uint64_t *)att, O, out_offs, status);
-    e = hipGetLastError();
+    e = rr_launch_scan_u64(out_offs, n, S.lb2, S.err2, stream);
     if (e != hipSuccess) return e;
-    e = rr_launch_scan_u64(out_offs, n, lb2, err2, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(rdbzset_emit_kernel, dim3(wave_grid(n)), dim3(WPB * RR_WAVE), 0, stream, data, in_offs, n,
-                       (const uint32_t *)list, (const uint64_t *)att, O, (const uint64_t *)out_offs, out, out_cap, status,
-                       (const uint64_t *)err1, (const uint64_t *)err2, totals);
+    hipLaunchKernelGGL(rdbzset_emit_kernel, dim3(grid), dim3(WPB * RR_WAVE), 0, stream, data, in_offs, n,
+                       (const uint32_t *)S.list, (const uint64_t *)S.att, O, (const uint64_t *)out_offs, out, out_cap, status,
+                       (const uint64_t *)S.err1, (const uint64_t *)S.err2, totals);
     return hipGetLastError();
 }

@@ -23,7 +23,7 @@ import flat_forge as ff
 import aof_reference as ar
 
 WAVE = 64                                                 # RR_AOF_ITEMS_PER_CMD: a command is one wave round
-SHORT_BODY = 32                                           # rr_aof.hip: longer bodies go through wave_copy
+SHORT_BODY = 32                                           # rr_stage_device.h: longer bodies go through wave_copy
 L, SI, SH, HH, ZS, HZ, ZZ = (rr.T_LIST_QUICKLIST, rr.T_SET_INTSET, rr.T_SET_HT, rr.T_HASH_HT, rr.T_ZSET_SKIPLIST,
                              rr.T_HASH_ZIPLIST, rr.T_ZSET_ZIPLIST)
 AGGREGATES = (L, SI, SH, HH, ZS, HZ, ZZ)

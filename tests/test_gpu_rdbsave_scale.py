@@ -22,10 +22,10 @@ from test_gpu_rdbsave import CANARY, _dev, check, list_edge_batch
 
 pytestmark = pytest.mark.gpu
 
-WPB = 4             # rr_rdbsave.hip:28, waves (values in flight) per workgroup
-GRID_CAP = 16384    # rr_rdbsave.hip:29, the grid's cap in workgroups
-LIST_GROUP = 8      # rr_rdbsave.hip:30, values a wave of rdb_list_kernel looks at per step
-SHORT_BODY = 32     # rr_rdbsave.hip:31, longer bodies go through wave_copy
+WPB = 4             # rr_rdbsave.hip, waves (values in flight) per workgroup
+GRID_CAP = 16384    # rr_rdbsave.hip, the grid's cap in workgroups
+LIST_GROUP = 8      # rr_rdbsave.hip, values a wave of rdb_list_kernel looks at per step
+SHORT_BODY = 32     # rr_stage_device.h, longer bodies go through wave_copy
 STRIDE_PLAIN = GRID_CAP * WPB               # values one step of rdb_size_kernel / rdb_emit_kernel covers
 STRIDE_LISTS = GRID_CAP * WPB * LIST_GROUP  # and one step of rdb_list_kernel<1> / <2>
 L = rr.T_LIST_QUICKLIST
