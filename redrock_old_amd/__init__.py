@@ -178,6 +178,12 @@ D2STRING_SLOT = 32              # the batch calls' bytes per text
 # include/rr_rdbzset.h (the small ZSets rdbconvert left because a score needs %.17g)
 RDBZSET_EXPORTS = ["rr_rdbzset_bound", "rr_rdbzset_batch", "rr_rdbzset_batch_host"]
 RDBZSET_SKIP = 55               # not attempted: not a ZSET_2 that rdbconvert left at RDBLOAD_E_CONVERT
+# include/rr_rdbloadall.h (the three load stages merged into one blob batch)
+RDBLOADALL_EXPORTS = ["rr_rdbmerge_batch", "rr_rdbloadall_caps", "rr_rdbloadall_ws_bytes", "rr_rdbloadall_batch",
+                      "rr_rdbloadall_batch_host"]
+RDBMERGE_E_SLICE = 57           # the holding stage's slice is reversed or past that batch's data_cap
+RDBMERGE_SPAN = 8192            # bytes of the output a wave of the merge's emit kernel owns at a time
+RDBMERGE_MAX_WAVES = 8192       # waves of that launch at most, a grid stride over the spans beyond
 # include/rr_aof.h (flat batch -> AOF rewrite commands, the AOF half of row f4)
 AOF_EXPORTS = ["rr_aof_bound", "rr_aof_select", "rr_aof_score_text", "rr_aof_batch", "rr_aof_batch_host"]
 AOF_E_CPU = 56                  # left to the CPU path: a ZLRAW-only ziplist, a score text that is not taken
@@ -306,6 +312,16 @@ def lib():
         L.rr_rdbzset_bound.restype = u64
         L.rr_rdbzset_batch.argtypes = [vp, C.POINTER(BlobBatch), vp, vp, C.POINTER(BlobBatch), vp, vp, C.POINTER(RdbLoadOpts), vp]
         L.rr_rdbzset_batch_host.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(RdbLoadOpts), vp, u64, vp, vp, C.POINTER(Totals)]
+    if "RR_LIB" not in os.environ or hasattr(L, "rr_rdbloadall_batch"):   # (RR_LIB: an older build may predate them)
+        bb = C.POINTER(BlobBatch)
+        L.rr_rdbmerge_batch.argtypes = [vp, bb, vp, bb, vp, vp, bb, vp, vp, bb, vp, vp, vp, vp]
+        L.rr_rdbloadall_caps.argtypes = [u64, u64, C.POINTER(u64)]
+        L.rr_rdbloadall_caps.restype = None
+        L.rr_rdbloadall_ws_bytes.argtypes = [u64, C.POINTER(u64)]
+        L.rr_rdbloadall_ws_bytes.restype = u64
+        L.rr_rdbloadall_batch.argtypes = [vp, bb, vp, vp, u64, C.POINTER(u64), bb, vp, vp, vp, vp, C.POINTER(RdbLoadOpts), vp]
+        L.rr_rdbloadall_batch_host.argtypes = [vp, vp, vp, vp, u64, C.POINTER(RdbLoadOpts), vp, u64, vp, vp, vp, vp,
+                                               C.POINTER(Totals)]
     if "RR_LIB" not in os.environ or hasattr(L, "rr_aof_batch"):   # (RR_LIB: an older build may predate them)
         L.rr_aof_bound.argtypes = [u64, u64, u64, u64]
         L.rr_aof_bound.restype = u64
@@ -878,6 +894,55 @@ class Engine:
                                         C.c_void_p(totals.data_ptr()), C.byref(opts) if opts is not None else None,
                                         _sp(stream)))
 
+    # ---- the three load stages merged into one blob batch (include/rr_rdbloadall.h) ---------------
+    def rdbloadall_host(self, data: np.ndarray, offsets: np.ndarray, types: np.ndarray, opts: RdbLoadOpts | None = None,
+                        out_cap: int | None = None):
+        """RDB payloads -> (blob data, offsets, out_types, status, stage_bytes, totals): rdbload, rdbconvert and
+        rdbzset merged into one batch.  out_cap None: asks for the size first (a call with out_cap 0)."""
+        n = len(offsets) - 1
+        data = np.ascontiguousarray(data, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        types = np.ascontiguousarray(types, np.uint8)
+        out_offsets = np.zeros(n + 1, np.uint64)
+        out_types = np.zeros(max(n, 1), np.uint8)
+        status = np.zeros(max(n, 1), np.uint8)
+        sb = np.zeros(3, np.uint64)
+        t = Totals()
+        po = C.byref(opts) if opts is not None else None
+        if out_cap is None:
+            _check(self._L.rr_rdbloadall_batch_host(self._ctx, _ptr(data), _ptr(offsets), _ptr(types), n, po, None, 0,
+                                                    _ptr(out_offsets), _ptr(out_types), _ptr(status), _ptr(sb), C.byref(t)))
+            out_cap = int(out_offsets[-1])
+        out = np.zeros(max(out_cap, 1), np.uint8)
+        _check(self._L.rr_rdbloadall_batch_host(self._ctx, _ptr(data), _ptr(offsets), _ptr(types), n, po, _ptr(out), out_cap,
+                                                _ptr(out_offsets), _ptr(out_types), _ptr(status), _ptr(sb), C.byref(t)))
+        return out[:min(int(out_offsets[-1]), out_cap)], out_offsets, out_types[:n], status[:n], sb, t.as_dict()
+
+    def rdbmerge(self, stage1, stage2, stage3, conv_types, types, out_data, out_offsets, out_types, status, totals, stream=None):
+        """rr_rdbmerge_batch on torch CUDA tensors; no host sync.  stage1 / stage2 / stage3: (data, offsets, status)
+        of rdbload, rdbconvert and rdbzset for the same values; out_data may be empty (sizes only), out_types None."""
+        n = out_offsets.numel() - 1
+        dp = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        bs = [BlobBatch(dp(d), o.data_ptr(), n, d.numel()) for d, o, _ in (stage1, stage2, stage3)]
+        outb = BlobBatch(dp(out_data), out_offsets.data_ptr(), n, out_data.numel())
+        _check(self._L.rr_rdbmerge_batch(self._ctx, C.byref(bs[0]), dp(stage1[2]), C.byref(bs[1]), dp(stage2[2]), dp(conv_types),
+                                         C.byref(bs[2]), dp(stage3[2]), dp(types), C.byref(outb), dp(out_types), dp(status),
+                                         C.c_void_p(totals.data_ptr()), _sp(stream)))
+
+    def rdbloadall(self, data, offsets, types, ws, stage_cap, out_data, out_offsets, out_types, status, stage_bytes, totals,
+                   opts: RdbLoadOpts | None = None, stream=None, ws_bytes: int | None = None):
+        """rr_rdbloadall_batch on torch CUDA tensors; no host sync.  ws: a uint8 workspace of rdbloadall_ws_bytes(n,
+        stage_cap) bytes; stage_cap: three ints (all zero: the sizing run); stage_bytes: int64[3]."""
+        n = out_offsets.numel() - 1
+        dp = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        inb = BlobBatch(dp(data), offsets.data_ptr(), n, data.numel())
+        outb = BlobBatch(dp(out_data), out_offsets.data_ptr(), n, out_data.numel())
+        caps = (C.c_uint64 * 3)(*[int(x) for x in stage_cap])
+        _check(self._L.rr_rdbloadall_batch(self._ctx, C.byref(inb), dp(types), C.c_void_p(ws.data_ptr()),
+                                           ws.numel() if ws_bytes is None else ws_bytes, caps, C.byref(outb), dp(out_types),
+                                           dp(status), C.c_void_p(stage_bytes.data_ptr()), C.c_void_p(totals.data_ptr()),
+                                           C.byref(opts) if opts is not None else None, _sp(stream)))
+
     # ---- AOF rewrite commands (include/rr_aof.h) --------------------------------------------------
     def aof_host(self, values: np.ndarray, elems: np.ndarray, arena: np.ndarray, key_data, key_offsets, expires=None,
                  data_cap: int | None = None, key_bytes: int | None = None):
@@ -1184,6 +1249,18 @@ def aof_score_text(text: bytes):
 def rdbzset_bound(n: int, payload_bytes: int) -> int:
     """rr_rdbzset_bound: an upper bound on the blob bytes of n ZSET_2 payloads converted with printed scores."""
     return int(lib().rr_rdbzset_bound(n, payload_bytes))
+
+
+def rdbloadall_caps(n: int, payload_bytes: int) -> tuple[int, int, int]:
+    """rr_rdbloadall_caps: the three stages' bounds (rdbload_bound, rdbconvert_bound, rdbzset_bound)."""
+    caps = (C.c_uint64 * 3)()
+    lib().rr_rdbloadall_caps(n, payload_bytes, caps)
+    return int(caps[0]), int(caps[1]), int(caps[2])
+
+
+def rdbloadall_ws_bytes(n: int, stage_cap) -> int:
+    """rr_rdbloadall_ws_bytes: the one call's workspace for n values and these three stage capacities."""
+    return int(lib().rr_rdbloadall_ws_bytes(n, (C.c_uint64 * 3)(*[int(x) for x in stage_cap])))
 
 
 def rdbconvert_bound(n: int, payload_bytes: int) -> int:

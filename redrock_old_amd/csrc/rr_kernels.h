@@ -114,6 +114,17 @@ uint64_t rr_rdbzset_scratch_words(uint64_t n);
 hipError_t rr_launch_rdbzset(const uint8_t *data, uint64_t in_cap, const uint64_t *in_offs, const uint8_t *types,
                              const uint8_t *convert_status, uint64_t n, const uint32_t *opt6, uint8_t *out, uint64_t out_cap,
                              uint64_t *out_offs, uint8_t *status, uint64_t *scratch, rr_totals *totals, hipStream_t stream);
+/* rr_rdbmerge.hip (include/rr_rdbloadall.h): the stage over the three load stages' batches (host
+ * structs of device pointers, read at the launch), a thread a value for the sizes and a wave a span
+ * of the output for the gather; scratch of rr_rdbmerge_scratch_words(n).  The second launch copies
+ * the three batches' offsets[n] to dst[0..3) */
+uint64_t rr_rdbmerge_scratch_words(uint64_t n);
+hipError_t rr_launch_rdbmerge(const rr_blob_batch *in1, const uint8_t *s1, const rr_blob_batch *in2, const uint8_t *s2,
+                              const uint8_t *conv_types, const rr_blob_batch *in3, const uint8_t *s3, const uint8_t *types,
+                              uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *out_offs, uint8_t *out_types, uint8_t *status,
+                              uint64_t *scratch, rr_totals *totals, hipStream_t stream);
+hipError_t rr_launch_rdbmerge_stage_bytes(const uint64_t *o1, const uint64_t *o2, const uint64_t *o3, uint64_t n, uint64_t *dst,
+                                          hipStream_t stream);
 /* rr_aof.hip (include/rr_aof.h): the stage; scratch of rr_aof_scratch_words(n).  expires may
  * be NULL; every other pointer on the device */
 uint64_t rr_aof_scratch_words(uint64_t n);
